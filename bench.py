@@ -24,7 +24,15 @@ each rank's batch by a padded-frame budget instead (``mi355x.frames_per_gpu``, t
 same per-GPU batch semantics ``train.py`` uses when that key is set; without it
 ``train.py`` splits ``batch_size`` across ranks -- the reference's global batch).
 
-Synthesis (``synth_rtf`` field, BASELINE's second metric): text ids -> int16 wav
+A plain run does the training measurement only: set-up, warm-up, the K timed steps,
+the output dump if asked for, the result line.  ``--dump-outputs DIR`` writes what the
+last timed step returned to its caller (``Trainer.train_step``: loss terms, model
+outputs, learning rate) as ``DIR/<name>.npy`` (float32; integers and masks float64;
+large arrays as a fixed seeded sample, under 64 MB in all).  Model, data and dropout
+seeds are fixed, so two builds run with the same arguments can be compared array by
+array.  Everything below is measured only with ``--full``.
+
+Synthesis (``--full``; ``synth_rtf`` field, BASELINE's second metric): text ids -> int16 wav
 through FastSpeech2 + style encoder (``--synth-config``, default BC2013_GST = the
 GST reference encoder + style-token attention on a reference mel, BASELINE #5) +
 HiFi-GAN V1, batch 256 per GPU over ``--synth-steps`` distinct batches, independent
@@ -59,6 +67,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the synthesis phases (synth_rtf, synth_rtf_b1, synth.rtf_also); a plain run "
+                         "measures the training headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed training step returned (loss terms, "
+                         "model outputs, learning rate) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--config", default="LJSpeech")
     ap.add_argument("--batch", type=int, default=None, help="utterances per GPU (default: config batch_size)")
     ap.add_argument("--pool", type=int, default=8, help="distinct synthetic batches cycled through")
@@ -142,7 +156,7 @@ def run(args):
     comm = torch.distributed.get_backend() if world > 1 else None
 
     tr = B.train_phase(args, rank, world, device)
-    sy = B.synth_phase(args, rank, world, device) if args.synth_steps > 0 else None
+    sy = B.synth_phase(args, rank, world, device) if (args.full and args.synth_steps > 0) else None
     sy2 = None
     if sy is not None and args.synth_also and args.synth_also != args.synth_config:
         import copy

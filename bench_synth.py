@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Synthesis benchmark alone: real-time factor of text ids -> int16 waveform.
 
-Same measurement as the ``synth_rtf`` field of ``bench.py`` (FastSpeech2 + style
+Same measurement as the ``synth_rtf`` field of ``bench.py --full`` (FastSpeech2 + style
 encoder on a reference mel + HiFi-GAN V1, int16 on the device, batch 256 per
 GPU; see ``speakingstyle_amd/benchmark.py``), without the training phase -- for
 profiling the inference path (``tools/gpu.sh synthprof``).  ``--gpus N`` starts

@@ -5,9 +5,10 @@ Two measurements (BASELINE.json: "train mel-frames/sec (node) + synth RTF"):
 * ``train_phase`` -- W untimed + K timed full training steps of FastSpeech2
   (forward + loss + backward + bucketed RCCL gradient all-reduce + clip + Adam +
   LR schedule) on synthetic LJSpeech-shaped batches; value = valid mel frames
-  summed over ranks / max-over-ranks wall time.
-* ``synth_phase`` -- text ids -> int16 waveform with the style encoder in the
-  loop (FastSpeech2 + FiLM reference encoder or GST on a reference mel, +
+  summed over ranks / max-over-ranks wall time.  ``dump_outputs`` writes what the last timed
+  step returned (``bench.py --dump-outputs``).
+* ``synth_phase`` (``bench.py --full``, ``bench_synth.py``) -- text ids -> int16
+  waveform with the style encoder in the loop (FastSpeech2 + FiLM reference encoder or GST on a reference mel, +
   HiFi-GAN V1 generator, int16 conversion on the device), batch 256 per GPU;
   RTF = max-over-ranks wall time / seconds of audio summed over ranks.  The
   random-init duration predictor would emit ~0 frames, so its
@@ -95,6 +96,39 @@ def tiny_overrides(mc):
                          attn_head=2)
 
 
+# ---------------------------------------------------------------------- outputs
+DUMP_BUDGET_BYTES = 48 << 20  # all files of one dump together (the arrays are written as float32 / float64)
+
+
+def dump_outputs(out_dir, result):
+    """Write what ``Trainer.train_step`` returned -- ``(losses, output, lr)`` -- as ``out_dir/<name>.npy``:
+    ``loss_<i>`` (the loss terms), ``output_<i>`` (the tensors of the model's output tuple, by position) and
+    ``lr``.  Floating-point tensors are stored as float32, integer and boolean ones as float64 (exact).  An
+    array over its share of the byte budget is stored as a fixed sample: the elements at seeded, sorted
+    flat indices, which depend on the arrays' sizes alone, so two builds store the same elements."""
+    import torch
+
+    losses, output, lr = result
+    named = [(f"loss_{i}", t) for i, t in enumerate(losses)]
+    named += [(f"output_{i}", t) for i, t in enumerate(output)]
+    named = [(n, t.detach()) for n, t in named if isinstance(t, torch.Tensor)]
+    os.makedirs(out_dir, exist_ok=True)
+    if lr is not None:
+        np.save(os.path.join(out_dir, "lr.npy"), np.asarray(float(lr), dtype=np.float64))
+    item = {n: (4 if t.is_floating_point() else 8) for n, t in named}
+    left = DUMP_BUDGET_BYTES
+    # smallest first: an array under the even share of what is left is stored whole and leaves the rest to the others
+    for k, (name, t) in enumerate(sorted(named, key=lambda e: e[1].numel() * item[e[0]])):
+        exact = not t.is_floating_point()
+        cap = left // (len(named) - k) // item[name]
+        left -= min(cap, t.numel()) * item[name]
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(t.numel()).choice(t.numel(), size=cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float64 if exact else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ---------------------------------------------------------------------- training
 def train_phase(args, rank, world, device):
     import torch
@@ -143,11 +177,13 @@ def train_phase(args, rank, world, device):
     from . import experimental
 
     fail_rank = experimental.get("fail_rank")  # fault injection (launcher failure-path test)
-    def step(i):
+    def step(i, keep=None):
         if fail_rank is not None and int(fail_rank) == rank and i == 1:
             raise RuntimeError(f"injected failure on rank {rank}")
         b, frames = pool[i % len(pool)]
-        trainer.train_step(b)
+        r = trainer.train_step(b)
+        if keep is not None:
+            keep.append(r)
         return frames
 
     # at least one untimed step under DP: the gradient-bucket calibration pass (ddp.GradBuckets)
@@ -206,9 +242,13 @@ def train_phase(args, rank, world, device):
             return r
 
         trainer.opt.arena.finalize_grads, trainer.opt.step_and_update_lr = fin, opt
+    dump_dir = getattr(args, "dump_outputs", None)
+    last = None  # what train_step returned in the last timed step (--dump-outputs); earlier steps' results are dropped
     for i in range(args.steps):
         h0 = time.perf_counter()
-        frames += step(warm + i)
+        if dump_dir and i == args.steps - 1:
+            last = []
+        frames += step(warm + i, last)
         host += time.perf_counter() - h0
         if lead:
             e = torch.cuda.Event(enable_timing=True)
@@ -221,6 +261,9 @@ def train_phase(args, rank, world, device):
     elapsed = time.perf_counter() - t0
     elapsed, frames_all = _max_sum(world, device, elapsed, float(frames))
     phases = trainer.timer.summary()
+    if last and rank == 0:
+        dump_outputs(dump_dir, last[0])
+    last = None
     info = {
         "phases": phases,
         "elapsed": elapsed, "frames": frames_all, "batch": batch, "warmup": warm,

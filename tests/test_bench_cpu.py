@@ -39,7 +39,7 @@ def _expected_frames(world, steps=2, warm=1, batch=3, pool=3):
 
 
 def test_bench_launches_two_ranks():
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--synth-batch", "2", "--synth-steps", "2",
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", "--synth-batch", "2", "--synth-steps", "2",
                         "--synth-b1-runs", "3"] + ARGS,
                        cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -65,6 +65,54 @@ def test_bench_single_process_default():
     assert rec["n_gpus"] == 1 and "synth_rtf" not in rec
     frames = rec["value"] * rec["ms_per_step"] * rec["steps"] / 1000.0
     np.testing.assert_allclose(frames, _expected_frames(1, warm=1), rtol=2e-3)
+
+
+def test_bench_plain_run_and_output_dump(tmp_path):
+    """Without ``--full`` the synthesis options are inert (training headline only); ``--dump-outputs`` writes the
+    last timed step's results as float32 / float64 .npy files, the same from run to run."""
+    dumps = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--synth-batch", "2", "--synth-steps", "2",
+                            "--dump-outputs", str(tmp_path / d)] + ARGS, cwd=ROOT, env=_env(),
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = json.loads(r.stdout.strip().splitlines()[-1])
+        assert "synth_rtf" not in rec and "synth" not in rec
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["unit"] == "mel-frames/s"
+        files = sorted(os.listdir(tmp_path / d))
+        dumps.append({f: np.load(tmp_path / d / f) for f in files})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and "lr.npy" in a
+    assert sum(1 for f in a if f.startswith("loss_")) == 6 and "output_0.npy" in a and "output_1.npy" in a
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), f
+        assert np.isfinite(a[f]).all(), f
+        np.testing.assert_allclose(a[f], b[f], rtol=1e-5, atol=1e-6, err_msg=f)
+    assert a["output_1.npy"].ndim == 3 and a["output_1.npy"].shape[0] == 3  # [batch, frames, mel bins]
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    import torch
+
+    from speakingstyle_amd import benchmark as B
+
+    monkeypatch.setattr(B, "DUMP_BUDGET_BYTES", 4096)
+    big = torch.arange(10000, dtype=torch.float32).reshape(100, 100)
+    mask = torch.arange(10000).reshape(100, 100) % 2 == 0
+    result = ([torch.tensor(1.5)], (big, None, mask, 7), 1e-3)
+    B.dump_outputs(str(tmp_path / "a"), result)
+    B.dump_outputs(str(tmp_path / "b"), result)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["loss_0.npy", "lr.npy", "output_0.npy", "output_2.npy"]
+    assert got["loss_0.npy"] == np.float32(1.5) and got["lr.npy"] == 1e-3
+    o0, o2 = got["output_0.npy"], got["output_2.npy"]
+    # the scalar is stored whole (4 bytes); the two large arrays share what is left evenly
+    assert o0.dtype == np.float32 and o0.shape == (4092 // 2 // 4,) and (np.diff(o0) > 0).all()  # sorted flat indices
+    assert o2.dtype == np.float64 and o2.shape == (2048 // 8,) and set(np.unique(o2)) <= {0.0, 1.0}
+    assert sum(v.nbytes for v in got.values()) <= 4096 + 8  # + lr
+    for f in got:
+        np.testing.assert_array_equal(got[f], np.load(tmp_path / "b" / f))
 
 
 def test_bench_failing_rank_exits_nonzero():

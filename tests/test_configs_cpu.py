@@ -16,7 +16,8 @@ import yaml
 
 from speakingstyle_amd.config import config_dir_triplet, load_configs, load_yaml
 
-REF = "/root/reference/config"
+# the reference's YAML settings, stored as fixtures
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_config")
 REF_NAMES = ["LJSpeech", "LJSpeech_paper", "LibriTTS", "AISHELL3", "BC2013"]
 ALL_NAMES = REF_NAMES + ["BC2013_GST"]
 
@@ -41,7 +42,6 @@ def _allowed(fname, key):
     return False
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
 @pytest.mark.parametrize("name", REF_NAMES)
 def test_config_matches_reference(name):
     ours = config_dir_triplet(name)

@@ -12,7 +12,7 @@ from speakingstyle_amd.text import g2p, text_to_sequence
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEX = os.path.join(ROOT, "lexicon", "pinyin-lexicon-r.txt")
-VAL = "/root/reference/preprocessed_data/AISHELL3/val.txt"
+VAL = os.path.join(ROOT, "tests", "golden", "AISHELL3", "val.txt")  # the reference's preprocessed AISHELL3 val.txt
 
 
 def _alternatives():
@@ -32,7 +32,6 @@ def test_lexicon_shipped_and_first_entry_wins():
     assert lex["ni3"] == ["n", "i3"]
 
 
-@pytest.mark.skipif(not os.path.exists(VAL), reason="reference AISHELL3 val.txt fixture not present")
 def test_val_pinyin_maps_to_phones():
     lex = g2p.load_lexicon(LEX, "zh")
     alts = _alternatives()
