@@ -402,6 +402,33 @@ SSAMD_API int ssamd_pack_info(const int64_t* lens, int B, int M, int64_t* cu, in
   return (int)hipGetLastError();
 }
 
+// x [B, T, C] bf16, in place: rows t >= lens[b] of sequence b set to 0 (16-B stores; C % 8 == 0).  The variance
+// adaptor's k = 3 convs read across the end of a sequence padded inside a longer text bucket: with the pad rows
+// zero they see what they see at the end of an unpadded text (FastSpeech2.infer_front, exact_pad).
+namespace {
+__global__ void __launch_bounds__(256) mask_pad_rows_kernel(bf16_t* __restrict__ x, const int64_t* __restrict__ lens,
+                                                            int T, int C8) {
+  const int b = blockIdx.y;
+  const long len = lens[b];
+  const long n = (long)T * C8;
+  const short8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  short8* xb = reinterpret_cast<short8*>(x) + (long)b * n;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    if (i / C8 >= len) xb[i] = z;
+  }
+}
+}  // namespace
+
+SSAMD_API int ssamd_mask_pad_rows(bf16_t* x, const int64_t* lens, int B, int T, int C, hipStream_t s) {
+  if (C % 8 || C <= 0) return -1;
+  if (B <= 0 || T <= 0) return 0;
+  if (!x || !lens) return -2;
+  const long n = (long)T * (C / 8);
+  const int gx = (int)((n + 255) / 256 < 64 ? (n + 255) / 256 : 64);
+  hipLaunchKernelGGL(mask_pad_rows_kernel, dim3(gx, B), dim3(256), 0, s, x, lens, T, C / 8);
+  return (int)hipGetLastError();
+}
+
 SSAMD_API int ssamd_embed_fwd(int mode, const int64_t* ids, const float* vals, const float* bins, int nbins,
                               const bf16_t* table, const bf16_t* addend, int L, bf16_t* out, int* idx_out, long rows,
                               int C, hipStream_t s) {

@@ -1193,6 +1193,101 @@ SSAMD_API int ssamd_voc_pack(const void* src, int src_f32, const int* cu, int B,
   return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------- capacity (bucketed) tables
+// One captured synthesis graph serves every utterance that fits its bucket (infer/graphs.py, bucketed mode): the
+// packed stages run at a fixed capacity of Rcap rows in nreal + 1 sequences of at most Mcap frames, the last one a
+// filler that takes the rows the real utterances leave over.  This kernel is the first node of that graph: from the
+// device mel lengths of the nreal real utterances it
+//   * clamps them so that nothing downstream can point past Rcap rows or Mcap frames, whatever bucket the host chose
+//     (len[b] = min(max(mel_len[b], 0), Mcap, rows left with one kept for the filler); F = min(Rcap - sum, Mcap)),
+//   * writes them back (mel_len[0 .. nreal], mel_len[nreal] = F) and rewrites the filler's durations to {F, 0, ...},
+//   * writes cu (int32 [nreal + 2]) and every tile table of the tiled kernels: geometry g = {rate, tile rows, n_cap,
+//     offset}; its first entries are the VocPack tiles of the nreal + 1 sequences in VocPack order, the rest up to
+//     n_cap null tiles {0, 0, 0, 0} (T = 0: every load and store of the tiled kernels is guarded by t < T).
+// The clamp is idempotent, so a block that reads a length the bookkeeping block has already written back computes
+// the same tables.
+namespace {
+constexpr int VCT_MAXSEQ = 64;
+constexpr int VCT_MAXGEOM = 32;
+struct CapGeoms {
+  int4 g[VCT_MAXGEOM];  // {rate, tile rows, n_cap, offset (int32 words) into buf}
+};
+
+__global__ void __launch_bounds__(256) voc_cap_tables_kernel(int64_t* __restrict__ mel_len, int64_t* __restrict__ dur,
+                                                             int nreal, int Tb, int Rcap, int Mcap, CapGeoms geoms,
+                                                             int ngeom, int* __restrict__ buf) {
+  __shared__ int len[VCT_MAXSEQ], cu[VCT_MAXSEQ + 1], first[VCT_MAXSEQ + 1];
+  const int nseq = nreal + 1;
+  const int g = blockIdx.y;
+  if (threadIdx.x == 0) {
+    int room = Rcap - 1, sum = 0;  // one row is always the filler's
+    for (int b = 0; b < nreal; ++b) {
+      long v = mel_len[b];
+      v = v < 0 ? 0 : v;
+      v = v > Mcap ? Mcap : v;
+      v = v > room ? room : v;
+      len[b] = (int)v;
+      room -= (int)v;
+      sum += (int)v;
+    }
+    const int F = Rcap - sum;
+    len[nreal] = F > Mcap ? Mcap : F;
+    cu[0] = 0;
+    for (int b = 0; b < nseq; ++b) cu[b + 1] = cu[b] + len[b];
+    if (g < ngeom) {
+      const int rate = geoms.g[g].x, bm = geoms.g[g].y;
+      first[0] = 0;
+      for (int b = 0; b < nseq; ++b) first[b + 1] = first[b] + (int)(((long)len[b] * rate + bm - 1) / bm);
+    }
+  }
+  __syncthreads();
+  if (g == ngeom) {  // the bookkeeping block row
+    if (blockIdx.x) return;
+    int* cu_out = buf;
+    for (int i = threadIdx.x; i <= nseq; i += 256) cu_out[i] = cu[i];
+    for (int i = threadIdx.x; i < nseq; i += 256) mel_len[i] = len[i];
+    int64_t* df = dur + (long)nreal * Tb;
+    for (int i = threadIdx.x; i < Tb; i += 256) df[i] = i ? 0 : len[nreal];
+    return;
+  }
+  const int rate = geoms.g[g].x, bm = geoms.g[g].y, ncap = geoms.g[g].z;
+  int4* tab = reinterpret_cast<int4*>(buf + geoms.g[g].w);
+  const int nt = first[nseq];
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < ncap; i += gridDim.x * 256) {
+    int4 e = make_int4(0, 0, 0, 0);
+    if (i < nt) {
+      int u = 0;
+      while (u + 1 < nseq && first[u + 1] <= i) ++u;
+      e = make_int4(cu[u] * rate, len[u] * rate, (i - first[u]) * bm, u);
+    }
+    tab[i] = e;
+  }
+}
+}  // namespace
+
+// mel_len int64 [nreal + 1] and dur int64 [nreal + 1, Tb] (device, rewritten in place); geoms: HOST int32 [ngeom, 4]
+// {rate, tile rows, n_cap, offset}; buf: device int32 [buf_words], cu at its start.  Every table must lie inside buf
+// behind cu on a 16-byte boundary, and Rcap * rate must fit int32: -2 otherwise (nothing is launched).
+SSAMD_API int ssamd_voc_cap_tables(int64_t* mel_len, int64_t* dur, int nreal, int Tb, int Rcap, int Mcap,
+                                   const int* geoms, int ngeom, int* buf, long buf_words, hipStream_t s) {
+  if (!mel_len || !dur || !buf || nreal < 0 || nreal + 1 > VCT_MAXSEQ || Tb < 1 || Rcap < 1 || Mcap < 1) return -2;
+  if (ngeom < 0 || ngeom > VCT_MAXGEOM || (ngeom && !geoms) || buf_words < nreal + 2) return -2;
+  if (reinterpret_cast<uintptr_t>(buf) % 16) return -2;
+  CapGeoms cg;
+  int max_cap = 1;
+  for (int i = 0; i < ngeom; ++i) {
+    const int rate = geoms[4 * i], bm = geoms[4 * i + 1], ncap = geoms[4 * i + 2], off = geoms[4 * i + 3];
+    if (rate < 1 || bm < 1 || ncap < 0 || off < nreal + 2 || off % 4) return -2;
+    if ((long)off + 4L * ncap > buf_words || (long)Rcap * rate > 0x7fffffffL) return -2;
+    cg.g[i] = make_int4(rate, bm, ncap, off);
+    if (ncap > max_cap) max_cap = ncap;
+  }
+  const int gx = (max_cap + 255) / 256 < 64 ? (max_cap + 255) / 256 : 64;
+  hipLaunchKernelGGL(voc_cap_tables_kernel, dim3(gx, ngeom + 1), dim3(256), 0, s, mel_len, dur, nreal, Tb, Rcap, Mcap,
+                     cg, ngeom, buf);
+  return (int)hipGetLastError();
+}
+
 SSAMD_API int ssamd_resblock_layer_pk(const bf16_t* x, const bf16_t* w1, const float* b1, const bf16_t* w2,
                                       const float* b2, const bf16_t* acc_in, bf16_t* out, const int* tt, int ntt, int C,
                                       int K, int d, float slope, float out_scale, int post_lrelu, hipStream_t s) {

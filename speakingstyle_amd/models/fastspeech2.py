@@ -153,11 +153,14 @@ class VariancePredictor(nn.Module):
         self.linear_layer = nn.Linear(fs, 1)
 
     def forward(self, x, lengths, style=None):
+        return self.rest(self.first(x), lengths, style)
+
+    def first(self, x):
+        """The first block: conv 1 -> ReLU -> LN -> dropout."""
         cl = self.conv_layer
         c1 = cl.conv1d_1
-        h = ops.conv_relu_layernorm(x, c1.conv.weight, c1.conv.bias, c1.pad, c1.dil, cl.layer_norm_1.weight,
-                                    cl.layer_norm_1.bias, post_drop=self.dropout, training=self.training)
-        return self.rest(h, lengths, style)
+        return ops.conv_relu_layernorm(x, c1.conv.weight, c1.conv.bias, c1.pad, c1.dil, cl.layer_norm_1.weight,
+                                       cl.layer_norm_1.bias, post_drop=self.dropout, training=self.training)
 
     def first_block(self):
         """(conv weight, conv bias, (LN weight, LN bias)) of the first conv block (fused with another
@@ -235,8 +238,19 @@ class VarianceAdaptor(nn.Module):
         return self.pitch_feature_level == "phoneme_level" and self.energy_feature_level == "phoneme_level"
 
     def forward(self, x, src_lens, mel_lens=None, max_len=None, pitch_target=None, energy_target=None,
-                duration_target=None, p_control=1.0, e_control=1.0, d_control=1.0, style=None, regulate=True):
+                duration_target=None, p_control=1.0, e_control=1.0, d_control=1.0, style=None, regulate=True,
+                exact_pad=False):
+        """``exact_pad`` (inference on the unregulated path): every tensor a k = 3 predictor conv reads has its rows
+        past ``src_lens`` zeroed first, so a text padded inside a longer bucket gets the predictions of the unpadded
+        text (the reference lets the speaker / pitch embeddings and the LayerNorm output of the pad rows leak into
+        the last phonemes of the shorter texts of a batch, and so does every other path here)."""
         p_pred = e_pred = None
+        assert not exact_pad or (not regulate and not self.training), "exact_pad: the packed inference path only"
+
+        def mp(t):
+            return ops.mask_pad_rows_(t, src_lens) if exact_pad else t
+
+        x = mp(x)
         if self.pitch_feature_level == "phoneme_level":
             # duration and pitch predictors read the same x: their first conv blocks run as one GEMM
             dp, pp_ = self.duration_predictor, self.pitch_predictor
@@ -245,13 +259,15 @@ class VarianceAdaptor(nn.Module):
             c1 = dp.conv_layer.conv1d_1
             h_d, h_p = ops.dual_conv_relu_layernorm(x, (wd, wp), (bd, bp), c1.pad, c1.dil, (lnd, lnp),
                                                     post_drop=dp.dropout, training=self.training)
-            log_d = dp.rest(h_d, src_lens, style)
+            log_d = dp.rest(mp(h_d), src_lens, style)
             p_pred, x = self._variance(pp_, self.pitch_bins, self.pitch_embedding, x, pitch_target, src_lens, p_control,
-                                       h1=h_p)
+                                       h1=mp(h_p))
+            x = mp(x)
         else:
-            log_d = self.duration_predictor(x, src_lens, style)
+            log_d = self.duration_predictor.rest(mp(self.duration_predictor.first(x)), src_lens, style)
         if self.energy_feature_level == "phoneme_level":
-            e_pred, x = self._variance(self.energy_predictor, self.energy_bins, self.energy_embedding, x, energy_target, src_lens, e_control)
+            e_pred, x = self._variance(self.energy_predictor, self.energy_bins, self.energy_embedding, x, energy_target,
+                                       src_lens, e_control, h1=mp(self.energy_predictor.first(x)))
 
         if not regulate:  # the packed decoder regulates itself (Decoder.forward_packed)
             return x, p_pred, e_pred, log_d, duration_target, mel_lens
@@ -472,9 +488,12 @@ class FastSpeech2(nn.Module):
 
     @torch.no_grad()
     def infer_front(self, speakers, texts, src_lens, max_src_len, mels=None, mel_lens=None, max_mel_len=None,
-                    p_control=1.0, e_control=1.0, d_control=1.0, style_weights=None):
+                    p_control=1.0, e_control=1.0, d_control=1.0, style_weights=None, exact_pad=False):
         """``infer_packed`` up to the durations (no host sync, fixed shapes: HIP-graph capturable,
-        ``infer/graphs.py``) -> (x [B, T, d], rounded durations [B, T], mel_len [B], style)."""
+        ``infer/graphs.py``) -> (x [B, T, d], rounded durations [B, T], mel_len [B], style).
+
+        ``exact_pad``: for the ``pad_for_bucket`` inputs of a capacity run -- each row comes out as its unpadded
+        text would (``VarianceAdaptor.forward``); the encoder already masks its pad rows."""
         cd = self.compute_dtype
         dev = texts.device
         if mels is not None and max_mel_len is None:
@@ -488,16 +507,58 @@ class FastSpeech2(nn.Module):
                 spk = self.speaker_emb(speakers) + self.spker_embed_proj(self.spker_table[speakers])
                 x = ops.add_rowvec(x, spk)
         x, _, _, log_d, _, _ = self.variance_adaptor(x, src_lens, None, None, None, None, None, p_control,
-                                                     e_control, d_control, style, regulate=False)
+                                                     e_control, d_control, style, regulate=False,
+                                                     exact_pad=exact_pad)
         d_rounded, mel_len = ops.duration_round(log_d, src_lens, d_control)
         return x, d_rounded, mel_len, style
 
+    @staticmethod
+    def pad_text_bucket(T: int) -> int:
+        """Text capacity of the bucketed synthesis graphs: T rounded up to a multiple of 16, at least 16."""
+        return max(16, -(-int(T) // 16) * 16)
+
+    @staticmethod
     @torch.no_grad()
-    def infer_back(self, front, lens):
+    def pad_for_bucket(speakers, texts, src_lens, Tb, mels=None, mel_lens=None, style_weights=None, controls=()):
+        """The B + 1-row inputs of a capacity run (``infer_front`` then ``infer_back(..., cap=)``): the B real rows
+        padded to ``Tb`` phonemes with the pad id (``src_lens`` masks them as in any batch), plus the filler row --
+        ONE phoneme (utterance 0's first), ``src_len`` 1, utterance 0's speaker, reference mel and style weights.  It
+        becomes the sequence that takes up the capacity's unused frames.  Per-phoneme ``controls`` ([B, T] tensors)
+        are padded with 1.0; scalars pass through.
+        -> (speakers, texts, src_lens, mels, mel_lens, style_weights, controls)"""
+        B, T = texts.shape
+        assert T <= Tb, "pad_for_bucket: text longer than the bucket"
+        tp = texts.new_zeros(B + 1, Tb)
+        tp[:B, :T] = texts
+        tp[B, 0] = texts[0, 0]
+        sl = torch.cat([src_lens, src_lens.new_ones(1)])
+
+        def first_again(t):
+            return None if t is None else torch.cat([t, t[:1]])
+
+        cs = []
+        for c in controls:
+            if isinstance(c, torch.Tensor) and c.dim() == 2:
+                cp = c.new_ones(B + 1, Tb)
+                cp[:B, : c.shape[1]] = c[:, :Tb]
+                c = cp
+            cs.append(c)
+        return (first_again(speakers), tp, sl, first_again(mels), first_again(mel_lens),
+                first_again(style_weights), tuple(cs))
+
+    @torch.no_grad()
+    def infer_back(self, front, lens, cap=None):
         """``infer_packed`` after the durations, for host mel lengths ``lens`` (fixed shapes given lens:
-        capturable) -> post-net mel rows [R, n_mel] fp32."""
+        capturable) -> post-net mel rows [R, n_mel] fp32.
+
+        ``cap = (Rcap, Mcap)``: ``front`` is a ``pad_for_bucket`` front whose filler row has been sized on the device
+        (``hip.VocPackCap.update``: the device mel lengths then sum to Rcap, none above Mcap); ``lens`` is ignored
+        and the B + 1 sequences run at R = Rcap rows, M = Mcap frames -> [Rcap, n_mel]."""
         x, d_rounded, mel_len, style = front
-        M, R = max(lens) if lens else 0, sum(lens)
+        if cap is not None:
+            R, M = int(cap[0]), int(cap[1])
+        else:
+            M, R = max(lens) if lens else 0, sum(lens)
         x, dec_lens, pk = self.decoder.forward_packed(x, d_rounded, mel_len, M, R, style)
         mel = ops.linear(x, self.mel_linear.weight, self.mel_linear.bias).float()
         post = self.postnet.forward_packed(mel.to(self.compute_dtype), pk).float() + mel

@@ -504,31 +504,10 @@ class Generator(nn.Module):
         c_last = self.h.upsample_initial_channel // 2 ** self.num_upsamples
         return c_last in (8, 32) and all(self._ups_image(i) is not None for i in range(self.num_upsamples))
 
-    @torch.no_grad()
-    def infer_packed(self, mel: torch.Tensor, lengths, int16_scale=None, width=None) -> torch.Tensor:
-        """mel [B, M, n_mel] (padded, channel-last, fp32 / bf16) + host frame ``lengths`` -> wav [B, W] (W = ``width``
-        or max(lengths) * hop; int16 when ``int16_scale``), samples past ``lengths[b] * hop`` zero.
-
-        The utterances' valid frames are packed back to back ([R, C] rows per stage, ``hip.VocPack``) and every
-        kernel zero-pads each conv at the utterance's own ends (the GEMM stages through a per-row position table,
-        the tiled ResBlock / upsampler / conv_post kernels through per-tile tables whose tiles never straddle two
-        utterances), so each utterance is vocoded exactly as if alone -- the reference vocodes the padded batch
-        and trims (``utils/model.py:97-115``) -- with no padded rows at any stage and one launch per layer for the
-        whole batch (the length-bucketed ``infer`` pads each bucket to its longest utterance + the receptive radius:
-        ~10 % extra rows at 8 buckets, and 8x the launches)."""
+    def _packed_geoms(self, lens):
+        """Every (rate, tile height) the tiled kernels of ``infer_packed`` ask for at these frame lengths."""
         hip = ops._hip()
-        dev = mel.device
-        rows_in = mel.dim() == 2  # already packed [R, n_mel] rows in ``lengths`` order (FastSpeech2.infer_packed)
-        B = len(lengths) if rows_in else mel.shape[0]
-        lens = [max(0, int(v)) for v in lengths] if rows_in else [max(0, min(int(v), mel.shape[1])) for v in lengths]
-        if rows_in:
-            assert mel.shape[0] == sum(lens), "infer_packed: packed rows vs lengths"
-        hop = 1
-        for u in self.h.upsample_rates:
-            hop *= u
-        W = int(width) if width is not None else max(lens) * hop
         nk = self.num_kernels
-        # every (rate, tile height) the tiled kernels will ask for: one host-built table buffer, one H2D copy
         geoms, rate = [], 1
         for i in range(self.num_upsamples):
             up = self.ups[i]
@@ -544,7 +523,50 @@ class Generator(nn.Module):
                 geoms.extend(blk.packed_tiles(cout, rate, lens))
         c_last = self.h.upsample_initial_channel // 2 ** self.num_upsamples
         geoms.append((rate, hip.voc_tile_rows("post", c_last)))
-        vp = hip.voc_pack_for(lens, dev, geoms)
+        return geoms
+
+    def cap_pack(self, nreal: int, Rcap: int, Mcap: int, device):
+        """A capacity pack (``hip.VocPackCap``) for ``infer_packed(..., cap=)``: nreal utterances plus one filler in
+        Rcap rows, none longer than Mcap frames.  Kernel and tile choices come from the canonical lengths of
+        (nreal, Rcap), never from an utterance's."""
+        hip = ops._hip()
+        return hip.VocPackCap(nreal, Rcap, Mcap, device, self._packed_geoms(hip.cap_lens(nreal, Rcap)))
+
+    @torch.no_grad()
+    def infer_packed(self, mel: torch.Tensor, lengths, int16_scale=None, width=None, cap=None) -> torch.Tensor:
+        """mel [B, M, n_mel] (padded, channel-last, fp32 / bf16) + host frame ``lengths`` -> wav [B, W] (W = ``width``
+        or max(lengths) * hop; int16 when ``int16_scale``), samples past ``lengths[b] * hop`` zero.
+
+        ``cap`` (a ``cap_pack`` whose ``update`` has run on this batch's device lengths): mel is its [Rcap, n_mel]
+        packed rows, ``lengths`` is ignored (the lengths live on the device) and the result is [nreal + 1, Mcap * hop],
+        the filler's row last -- the same launches for every utterance of the bucket (``infer/graphs.py``).
+
+        The utterances' valid frames are packed back to back ([R, C] rows per stage, ``hip.VocPack``) and every
+        kernel zero-pads each conv at the utterance's own ends (the GEMM stages through a per-row position table,
+        the tiled ResBlock / upsampler / conv_post kernels through per-tile tables whose tiles never straddle two
+        utterances), so each utterance is vocoded exactly as if alone -- the reference vocodes the padded batch
+        and trims (``utils/model.py:97-115``) -- with no padded rows at any stage and one launch per layer for the
+        whole batch (the length-bucketed ``infer`` pads each bucket to its longest utterance + the receptive radius:
+        ~10 % extra rows at 8 buckets, and 8x the launches)."""
+        hip = ops._hip()
+        dev = mel.device
+        rows_in = mel.dim() == 2  # already packed [R, n_mel] rows in ``lengths`` order (FastSpeech2.infer_packed)
+        hop = 1
+        for u in self.h.upsample_rates:
+            hop *= u
+        nk = self.num_kernels
+        if cap is not None:
+            assert rows_in and mel.shape[0] == cap.R and width is None, "infer_packed: capacity rows"
+            vp, B, W = cap, cap.B, cap.M * hop
+        else:
+            B = len(lengths) if rows_in else mel.shape[0]
+            lens = [max(0, int(v)) for v in lengths] if rows_in else \
+                [max(0, min(int(v), mel.shape[1])) for v in lengths]
+            if rows_in:
+                assert mel.shape[0] == sum(lens), "infer_packed: packed rows vs lengths"
+            W = int(width) if width is not None else max(lens) * hop
+            # every (rate, tile height) the tiled kernels will ask for: one host-built table buffer, one H2D copy
+            vp = hip.voc_pack_for(lens, dev, self._packed_geoms(lens))
         out = torch.zeros(B, W, device=dev, dtype=torch.int16 if int16_scale is not None else torch.float32)
         if vp.R == 0:
             return out

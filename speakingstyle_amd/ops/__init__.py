@@ -240,6 +240,13 @@ def add_table_rows(x, table, ids):
     return x + F.embedding(ids, table).to(x.dtype).unsqueeze(1)
 
 
+def mask_pad_rows_(x, lengths):
+    """Inference only, in place where it can: x [B, L, C] with the rows t >= lengths[b] set to 0."""
+    if use_hip(x):  # bf16, contiguous, C % 8 == 0: anything else is an error there, not a torch pass
+        return _hip().mask_pad_rows_(x, lengths)
+    return x.masked_fill(ref.lengths_to_mask(lengths, x.shape[1]).unsqueeze(-1), 0.0)
+
+
 def pack_rows(x, pack: PackInfo, pe=None):
     """[B, M, C] -> packed [1, R, C] (+ positional encoding ``pe[t]`` when given)."""
     if use_hip(x):

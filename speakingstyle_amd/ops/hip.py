@@ -2419,6 +2419,152 @@ def voc_pack_for(lens, device, rate_tiles, cache: int = 32) -> "VocPack":
     return vp
 
 
+# ------------------------------------------------------------------------ capacity (bucketed) pack
+_SIGS.update({"ssamd_voc_cap_tables": [P, P, I, I, I, I, P, I, P, L_, P],
+              "ssamd_mask_pad_rows": [P, P, I, I, I, P]})
+
+
+def mask_pad_rows_(x, lengths):
+    """In place (inference): rows t >= lengths[b] of x [B, T, C] bf16 set to 0.  Returns x."""
+    _need(x, torch.bfloat16, "mask_pad_rows.x")
+    lens = lengths.to(torch.int64).contiguous()
+    B, T, C = x.shape
+    assert lens.numel() == B and lens.is_cuda, "mask_pad_rows: one device length per sequence"
+    _check(lib().ssamd_mask_pad_rows(_ptr(x), _ptr(lens), B, T, C, _stream()), "ssamd_mask_pad_rows")
+    return x
+
+# capacity ladder of the bucketed synthesis graphs (infer/graphs.py): steps of 64 up to 1024, 128 beyond.  Finer
+# steps waste fewer filler rows but need more graphs before a stream only replays.  First drafted with steps of 32
+# up to 512; the latency record (profiles/serve_b1_distinct.txt) argued for 64: a replay costs the same at either
+# step (batch 1 is launch-bound, <= 32 more filler frames are not measurable: replay-only median 1.96 ms both),
+# but after 30 utterances 11 of the next 30 still opened a bucket with steps of 32 (median 2.10 ms, p90 4.12) and
+# 1 of 30 with steps of 64 (median 1.97 ms, p90 2.25).
+_CAP_LADDER = ((1024, 64), (None, 128))
+
+
+def cap_ceil(n: int) -> int:
+    """Smallest ladder value >= n (at least one step)."""
+    n = max(1, int(n))
+    lo = 0
+    for top, step in _CAP_LADDER:
+        if top is None or n <= top:
+            return max(lo + step, lo + -(-(n - lo) // step) * step)
+        lo = top
+    raise AssertionError
+
+
+def cap_bucket(lens):
+    """(Rcap, Mcap) for these real mel lengths: Rcap rows hold every utterance plus at least one filler row, Mcap
+    frames hold the longest utterance and the filler (F = Rcap - sum(lens))."""
+    tot = sum(max(0, int(v)) for v in lens)
+    rcap = cap_ceil(tot + 1)
+    mcap = cap_ceil(max([max(0, int(v)) for v in lens] + [rcap - tot]))
+    return rcap, mcap
+
+
+def cap_lens(nreal: int, rcap: int):
+    """The canonical length set of a capacity: what kernel and tile selection see instead of the real lengths, so
+    that the launch, the table geometry and a captured graph depend on (nreal, Rcap) only."""
+    assert rcap > nreal >= 0
+    return [rcap - nreal] + [1] * nreal
+
+
+def cap_geoms(nreal: int, rcap: int, rate_tiles):
+    """[(rate, bm, n_cap, offset)] of a capacity buffer: cu (int32 [nreal + 2], padded to 16 bytes) then one table
+    of n_cap = ceil(Rcap * rate / bm) + nreal tiles per distinct (rate, bm) -- enough for ANY nreal + 1 lengths that
+    sum to Rcap, since sum_i ceil(x_i) <= ceil(sum_i x_i) + (n - 1).  Also returns the buffer's size in words."""
+    o = -(-(nreal + 2) // 4) * 4
+    out, seen = [], set()
+    for rate, bm in rate_tiles:
+        key = (int(rate), int(bm))
+        if key in seen or key[1] <= 0:
+            continue
+        seen.add(key)
+        n_cap = -(-rcap * key[0] // key[1]) + nreal
+        out.append((key[0], key[1], n_cap, o))
+        o += 4 * n_cap
+    return out, o
+
+
+def cap_tables_host(real_lens, Rcap, geoms, Mcap=None):
+    """Pure-numpy reference of ``ssamd_voc_cap_tables``: -> (lens int64 [nreal + 1] clamped, the filler last,
+    cu int32 [nreal + 2], {(rate, bm): int32 [n_cap, 4] table}).  ``geoms``: (rate, bm, n_cap, offset) tuples."""
+    import numpy as np
+
+    nreal = len(real_lens)
+    Mcap = int(Rcap) if Mcap is None else int(Mcap)
+    lens = np.zeros(nreal + 1, dtype=np.int64)
+    room = int(Rcap) - 1
+    for b, v in enumerate(real_lens):
+        lens[b] = min(max(int(v), 0), Mcap, room)
+        room -= int(lens[b])
+    lens[nreal] = min(int(Rcap) - int(lens[:nreal].sum()), Mcap)
+    cu = np.zeros(nreal + 2, dtype=np.int64)
+    cu[1:] = np.cumsum(lens)
+    tabs = {}
+    for rate, bm, n_cap, _ in geoms:
+        L = lens * rate
+        cnt = (L + bm - 1) // bm
+        tab = np.zeros((n_cap, 4), dtype=np.int32)
+        i = 0
+        for u in range(nreal + 1):
+            for k in range(int(cnt[u])):
+                if i < n_cap:
+                    tab[i] = (cu[u] * rate, L[u], k * bm, u)
+                i += 1
+        tabs[(int(rate), int(bm))] = tab
+    return lens, cu.astype(np.int32), tabs
+
+
+class VocPackCap:
+    """``VocPack`` of a capacity bucket: Rcap rows in nreal + 1 sequences of at most Mcap frames, whose tables are
+    written ON THE DEVICE by ``update`` (``ssamd_voc_cap_tables``) from the device mel lengths -- no host data per
+    utterance, so the launch sequence is the same for every utterance of the bucket and can be captured once.
+    ``lens`` is the canonical set (``cap_lens``); the real lengths exist on the device only.  The pack owns its
+    static buffers (tables, one rinfo table per rate); ``rinfo(rate)`` is rebuilt from ``cu`` once per ``update``,
+    inside the launch sequence.  Never cached in ``_VOC_PACKS``."""
+
+    def __init__(self, nreal, Rcap, Mcap, device, rate_tiles):
+        import numpy as np
+
+        self.nreal, self.R, self.M = int(nreal), int(Rcap), int(Mcap)
+        self.B = self.nreal + 1
+        self.lens = np.asarray(cap_lens(self.nreal, self.R), dtype=np.int64)
+        self.device = device
+        self.geoms, words = cap_geoms(self.nreal, self.R, rate_tiles)
+        self._geoms_host = torch.tensor(self.geoms, dtype=torch.int32).reshape(-1, 4).contiguous()
+        self._off = {(r, bm): (o, n) for r, bm, n, o in self.geoms}
+        self.buf = torch.zeros(words, device=device, dtype=torch.int32)
+        self.cu = self.buf[: self.B + 1]
+        self._rinfo, self._fresh = {}, set()
+
+    def update(self, mel_len, durations):
+        """First kernel of a run: mel_len int64 [nreal + 1] and durations int64 [nreal + 1, Tb] (device) get the
+        filler's length and durations (and the defensive clamp), cu and every tile table are rewritten."""
+        _need(mel_len, torch.int64, "cap.mel_len")
+        _need(durations, torch.int64, "cap.durations")
+        assert mel_len.numel() == self.B and durations.dim() == 2 and durations.shape[0] == self.B, "cap: rows"
+        rc = lib().ssamd_voc_cap_tables(_ptr(mel_len), _ptr(durations), self.nreal, durations.shape[1], self.R, self.M,
+                                        _ptr(self._geoms_host), len(self.geoms), _ptr(self.buf), self.buf.numel(),
+                                        _stream())
+        _check(rc, "ssamd_voc_cap_tables")
+        self._fresh.clear()
+
+    def tiles(self, rate, bm):
+        o, n = self._off[(int(rate), int(bm))]
+        return self.buf[o: o + 4 * n], n
+
+    def rinfo(self, rate):
+        r = self._rinfo.get(rate)
+        if r is None:  # zeros: {0, 0} rows pad every tap, should a clamped run leave rows behind the last sequence
+            r = self._rinfo[rate] = torch.zeros(self.R * rate, 2, device=self.device, dtype=torch.int32)
+        if rate not in self._fresh:
+            _check(lib().ssamd_voc_rinfo(_ptr(self.cu), self.B, int(rate), self.M * rate, _ptr(r), _stream()),
+                   "ssamd_voc_rinfo")
+            self._fresh.add(rate)
+        return r
+
+
 _TILE_ROWS = {}
 
 
@@ -2552,9 +2698,14 @@ def resblock_fused_packed(x, vp, rate, convs1, convs2, dilations, slope, acc=Non
     return out
 
 
-def conv3_sq_packed(x, vp, rate, wimg, bias):
+def conv3_sq_packed(x, vp, rate, wimg, bias, out=None):
+    """``conv3_sq`` on packed rows x [R*rate, C]; ``out``: a caller-owned [R*rate, C] bf16 buffer (not x)."""
     Rr, C = x.shape
-    out = torch.empty_like(x)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _need(out, torch.bfloat16, "conv3_sq_packed.out")
+        assert out.shape == x.shape and out.data_ptr() != x.data_ptr(), "conv3_sq_packed: out shape"
     tt, n = vp.tiles(rate, voc_tile_rows(2, C))
     _check(lib().ssamd_conv3_sq_pk(_ptr(x), _ptr(wimg), _ptr(bias), _ptr(out), _ptr(tt), n, C, _stream()),
            "ssamd_conv3_sq_pk")
@@ -2568,7 +2719,9 @@ def conv_post_packed(x, vp, rate, w, b, out, slope=0.01, int16_scale=None):
     wf = w.detach().reshape(-1).float().contiguous()
     bf = None if b is None else b.detach().reshape(-1).float().contiguous()
     tt, n = vp.tiles(rate, voc_tile_rows("post", C))
-    assert out.shape[0] == vp.B and out.shape[1] >= int(vp.lens.max()) * rate, "conv_post_packed: output shape"
+    longest = getattr(vp, "M", None)  # a capacity pack's sequences are bounded by its Mcap, not by ``lens``
+    longest = int(vp.lens.max()) if longest is None else longest
+    assert out.shape[0] == vp.B and out.shape[1] >= longest * rate, "conv_post_packed: output shape"
     if int16_scale is None:
         assert out.dtype == torch.float32
         rc = lib().ssamd_conv_post_pk(_ptr(x), _ptr(wf), _ptr(bf), _ptr(tt), n, C, float(slope), 1.0, _ptr(out), None,

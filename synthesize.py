@@ -6,6 +6,9 @@ prosody control and GST style weights.
   batch:   python synthesize.py --mode batch --source val.txt --restore_step N -p -m -t
   word-level control: --word_pitch 1,1.3,0.8 --word_energy ... --word_duration ... (one factor per word)
   GST:     --style_weights 0.5,0,0,...   (one weight per style token)
+  serve:   python synthesize.py --mode serve [--source lines.txt] --restore_step N -p -m -t
+           one text per line (from --source or stdin) -> {result_path}/serve_{line:04d}.wav, through the serving
+           entry (infer/serve.py: bucketed HIP graphs on the GPU); prints the graph statistics at the end
 """
 import argparse
 import os
@@ -28,10 +31,36 @@ def _floats(s):
     return None if s is None else [float(x) for x in s.split(",") if x.strip()]
 
 
+def serve(args):
+    """One wav per input line through ``infer.serve.Synthesizer``."""
+    from speakingstyle_amd.audio.io import write_wav
+    from speakingstyle_amd.infer.serve import Synthesizer
+
+    configs = load_configs(args.preprocess_config, args.model_config, args.train_config)
+    tts = Synthesizer(configs, args.restore_step)
+    result_path = args.result_path or configs[2]["path"]["result_path"]
+    os.makedirs(result_path, exist_ok=True)
+    if args.source is not None:
+        with open(args.source, encoding="utf-8") as f:
+            lines = f.read().splitlines()
+    else:
+        lines = sys.stdin.read().splitlines()
+    n = 0
+    for line in lines:
+        if not line.strip():
+            continue
+        wav = tts.tts(line.strip(), speaker_id=args.speaker_id, ref_audio=args.ref_audio,
+                      style_weights=_floats(args.style_weights), pitch_control=args.pitch_control,
+                      energy_control=args.energy_control, duration_control=args.duration_control)
+        write_wav(os.path.join(result_path, f"serve_{n:04d}.wav"), tts.sampling_rate, wav)
+        n += 1
+    print(f"wrote {n} wavs to {result_path}; graphs: {tts.stats}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--restore_step", type=int, required=True)
-    ap.add_argument("--mode", type=str, choices=["batch", "single"], required=True)
+    ap.add_argument("--mode", type=str, choices=["batch", "single", "serve"], required=True)
     ap.add_argument("--source", type=str, default=None)
     ap.add_argument("--text", type=str, default=None)
     ap.add_argument("--ref_audio", type=str, default=None)
@@ -50,6 +79,9 @@ def main(argv=None):
     ap.add_argument("--plot", action="store_true", help="also write mel/pitch/energy PNGs")
     ap.add_argument("--result_path", type=str, default=None)
     args = ap.parse_args(argv)
+    if args.mode == "serve":
+        assert args.text is None
+        return serve(args)
     if args.mode == "batch":
         assert args.source is not None and args.text is None
     else:
