@@ -116,6 +116,18 @@ def build_sanitized(verbose=False):
     return exes
 
 
+def build_blockmap_selftest():
+    """The attention block map (csrc/attn_blockmap.h) as plain host code under ASan+UBSan: returns the
+    self-test executable (csrc/selftest_attn_blockmap.cpp) in build/sanitize/."""
+    out_dir = os.path.join(ROOT, "build", "sanitize")
+    os.makedirs(out_dir, exist_ok=True)
+    test = os.path.join(HERE, "selftest_attn_blockmap.cpp")
+    exe = os.path.join(out_dir, "selftest_attn_blockmap")
+    if _stale(exe, [test, os.path.join(HERE, "attn_blockmap.h")]):
+        _run(["g++", "-O1", "-g", "-std=c++17", "-I", HERE] + SANITIZERS["asan"] + ["-o", exe, test])
+    return exe
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 4))

@@ -19,7 +19,11 @@
 //   dK^T += Q^T dS;  kernel dQ: per 64-query block, swapped again (query on the lane),
 //   dQ^T += K^T dS^T.  Every LDS image is XOR-swizzled for its read instruction
 //   (ds_read_b128 row reads / ds_read_b64_tr_b16 transposed reads).
+// Block placement (D = 128 LDS-DMA kernels): a 1-D grid mapped by attn_blockmap.h so that all
+//   blocks of one (b, h) -- which stream the same K/V (forward, dQ) or Q/dO (dK/dV) tiles -- run
+//   on one XCD and share its L2, sequences dealt round-robin over the XCDs.
 #include "common.h"
+#include "attn_blockmap.h"
 
 namespace {
 
@@ -323,10 +327,12 @@ template <int NF>
 __global__ void __launch_bounds__(NT, 2) attn_fwd_dma_kernel(const bf16_t* __restrict__ qkv, const int64_t* __restrict__ lens,
                                                       const int64_t* __restrict__ cu,
                                                       bf16_t* __restrict__ out, float* __restrict__ lse, int L, int H,
-                                                      float scale_log2) {
+                                                      float scale_log2, int BH, int gx, int xcd) {
   constexpr int D = 128;
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 x (K, V) tiles, unified swizzle
-  const int bh = blockIdx.y, b = bh / H, h = bh % H;
+  const AttnBlock blk = attn_block_map(blockIdx.x, gx, xcd);
+  if (blk.bh >= BH) return;
+  const int bh = blk.bh, xb = blk.x, b = bh / H, h = bh % H;
   const int RS = 3 * H * D;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4;
   const int len = (int)lens[b];
@@ -338,12 +344,12 @@ __global__ void __launch_bounds__(NT, 2) attn_fwd_dma_kernel(const bf16_t* __res
   const bf16_t* Vp = qkv + 2 * H * D + h * D;
   int qv[NF];
   short8 qf[NF][D / 32];
-  if (blockIdx.x * (64 * NF) >= len) {
+  if (xb * (64 * NF) >= len) {
     // query rows past the sequence length are defined as zero output (they are masked
     // downstream): a fully padded query block only writes zeros
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
-      const int q = blockIdx.x * (64 * NF) + wave * (16 * NF) + f * 16 + (lane & 15);
+      const int q = xb * (64 * NF) + wave * (16 * NF) + f * 16 + (lane & 15);
       if (q >= Lq) continue;
       bf16_t* op = out + (rowb + q) * (long)(H * D) + h * D;
 #pragma unroll
@@ -354,7 +360,7 @@ __global__ void __launch_bounds__(NT, 2) attn_fwd_dma_kernel(const bf16_t* __res
   }
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
-    qv[f] = blockIdx.x * (64 * NF) + wave * (16 * NF) + f * 16 + (lane & 15);
+    qv[f] = xb * (64 * NF) + wave * (16 * NF) + f * 16 + (lane & 15);
 #pragma unroll
     for (int s = 0; s < D / 32; ++s) {
       short8 v = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -627,19 +633,21 @@ __global__ void __launch_bounds__(NT, MINB) attn_bwd_dkdv_dma_kernel(const bf16_
                                                            const int64_t* __restrict__ cu,
                                                            const bf16_t* __restrict__ dO, const float* __restrict__ lse,
                                                            const float* __restrict__ delta, bf16_t* __restrict__ dqkv,
-                                                           int L, int H, float scale_log2, float scale) {
+                                                           int L, int H, float scale_log2, float scale, int BH, int gx, int xcd) {
   constexpr int D = 128;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // per buffer: Q image, dO image (unified swizzle, DMA'd), lse[64], delta[64]
   constexpr int BUFB = 2 * TQ * D * 2 + 2 * TQ * 4;
-  const int bh = blockIdx.y, b = bh / H, h = bh % H;
+  const AttnBlock blk = attn_block_map(blockIdx.x, gx, xcd);
+  if (blk.bh >= BH) return;
+  const int bh = blk.bh, xb = blk.x, b = bh / H, h = bh % H;
   const int RS = 3 * H * D, OS = H * D;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4;
   const int len = (int)lens[b];
   // packed variable-length rows (cu = row offsets): only rows < len exist for sequence b
   const long rowb = cu ? (long)cu[b] : (long)b * L;
   const int Lq = cu ? len : L;
-  const int kblk0 = blockIdx.x * (64 * NF);
+  const int kblk0 = xb * (64 * NF);
   auto load_ld = [&](int q0) -> float {  // thread t < 64: lse of query q0+t; 64 <= t < 128: delta
     const int qq = q0 + (tid & 63);
     if (tid >= 128) return 0.f;
@@ -931,11 +939,13 @@ __global__ void __launch_bounds__(NT, MINB) attn_bwd_dq_dma_kernel(const bf16_t*
                                                          const int64_t* __restrict__ cu,
                                                          const bf16_t* __restrict__ dO, const float* __restrict__ lse,
                                                          const float* __restrict__ delta, bf16_t* __restrict__ dqkv,
-                                                         int L, int H, float scale_log2, float scale) {
+                                                         int L, int H, float scale_log2, float scale, int BH, int gx, int xcd) {
   constexpr int D = 128;
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 x (K, V) unified images, DMA'd
   constexpr int BUFB = 2 * TK * D * 2;
-  const int bh = blockIdx.y, b = bh / H, h = bh % H;
+  const AttnBlock blk = attn_block_map(blockIdx.x, gx, xcd);
+  if (blk.bh >= BH) return;
+  const int bh = blk.bh, xb = blk.x, b = bh / H, h = bh % H;
   const int RS = 3 * H * D, OS = H * D;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4;
   const int len = (int)lens[b];
@@ -949,10 +959,10 @@ __global__ void __launch_bounds__(NT, MINB) attn_bwd_dq_dma_kernel(const bf16_t*
   int qv[NF];
   float lq[NF], dd[NF];
   short8 qf[NF][D / 32], df_[NF][D / 32];
-  if (blockIdx.x * (64 * NF) >= len) {  // padded query block: dQ = 0
+  if (xb * (64 * NF) >= len) {  // padded query block: dQ = 0
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
-      const int q = blockIdx.x * (64 * NF) + wave * (16 * NF) + f * 16 + (lane & 15);
+      const int q = xb * (64 * NF) + wave * (16 * NF) + f * 16 + (lane & 15);
       if (q >= Lq) continue;
       bf16_t* dqp = dqkv + (rowb + q) * RS + h * D;
 #pragma unroll
@@ -962,7 +972,7 @@ __global__ void __launch_bounds__(NT, MINB) attn_bwd_dq_dma_kernel(const bf16_t*
   }
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
-    qv[f] = blockIdx.x * (64 * NF) + wave * (16 * NF) + f * 16 + (lane & 15);
+    qv[f] = xb * (64 * NF) + wave * (16 * NF) + f * 16 + (lane & 15);
 #pragma unroll
     for (int s = 0; s < D / 32; ++s) {
       short8 a = {0, 0, 0, 0, 0, 0, 0, 0}, c = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1096,18 +1106,27 @@ SSAMD_API void ssamd_attn_set_nf32(int fwd, int bwd) {
   }
 
 static const float kLog2e = 1.4426950408889634f;
-static int g_fwd_dma = 1, g_fwd_nf = 2;  // measured (L=800, D=128): DMA NF=2 at 2 waves/SIMD 0.169 ms, DMA NF=1 0.227, registers 0.222
+static int g_fwd_dma = 1, g_fwd_nf = 2;  // measured (L=800, D=128, B=200): DMA NF=2 at 2 waves/SIMD 0.128 ms, DMA NF=1 0.170, registers 0.221
 SSAMD_API void ssamd_attn_set_fwd(int dma, int nf) {
   g_fwd_dma = dma;
   g_fwd_nf = nf;
 }
-static int g_nf_kv = 1, g_nf_q = 2;  // measured (D=128, L=800): LDS-DMA dK/dV NF=1 (2 waves/SIMD), LDS-DMA dQ NF=2: bwd 0.599 ms (from 0.793)
+static int g_nf_kv = 1, g_nf_q = 2;  // measured (D=128, L=800, B=200), bwd: LDS-DMA dK/dV NF=1 (2 waves/SIMD) 0.490 ms, NF=2 (1 wave/SIMD) 0.569, registers NF=2 0.595 (dQ NF=1)
 static int g_kv_dma = 1, g_q_dma = 1;
 SSAMD_API void ssamd_attn_set_kv_dma(int v) { g_kv_dma = v; }
+// sequence-to-XCD block placement of the D = 128 LDS-DMA kernels (attn_blockmap.h); 0: plain order.
+// Measured on the LJSpeech training step (profiles/r7_attn_ab.txt): L2 fetch per call 705 -> 153 MiB
+// (forward), 758 -> 207 (dQ), 888 -> 210 (dK/dV); kernels -13 / -10 / -7 %, step 24.63 -> 24.37 ms.
+// dK and dV as two NF = 2 single-accumulator passes (5 matmuls instead of 4) were measured there too
+// and lost to the fused NF = 1 kernel by 0.4 % of the step: alone on the GPU the fused kernel already
+// runs within 1.3x of the dQ kernel's time per matmul; its long time in a step trace is shared with
+// the side stream's weight-gradient kernels.
+static int g_xcd = 1;
+SSAMD_API void ssamd_attn_set_xcd(int v) { g_xcd = v; }
 SSAMD_API void ssamd_attn_set_q_dma(int v, int nf) {
   g_q_dma = v;
   g_nf_q = nf;
-}  // measured on MI355X (D=128): dK/dV NF=2, dQ NF=1 -> -14 %
+}  // measured (as above, dK/dV NF=1), bwd: LDS-DMA dQ NF=2 0.441 ms, NF=1 0.485, registers NF=1 0.510
 SSAMD_API void ssamd_attn_set_nf(int nf_kv, int nf_q) {
   g_nf_kv = nf_kv;
   g_nf_q = nf_q;
@@ -1137,14 +1156,15 @@ SSAMD_API int ssamd_attn_fwd(const bf16_t* qkv, const int64_t* lens, const int64
                              int L, int H, int D, float scale, hipStream_t s) {
   if ((long)B * L == 0) return 0;
   if (D == 128 && g_fwd_dma) {  // LDS-DMA K/V tiles, NF query fragments per wave
+    const int BH = B * H;
     if (g_fwd_nf == 2) {
-      dim3 grid(cdiv(L, 128), B * H);
-      hipLaunchKernelGGL((attn_fwd_dma_kernel<2>), grid, dim3(NT), 4 * TK * 128 * 2, s, qkv, lens, cu, out, lse, L,
-                         H, scale * kLog2e);
+      const int gx = cdiv(L, 128);
+      hipLaunchKernelGGL((attn_fwd_dma_kernel<2>), dim3(attn_map_grid(gx, BH)), dim3(NT), 4 * TK * 128 * 2, s, qkv,
+                         lens, cu, out, lse, L, H, scale * kLog2e, BH, gx, g_xcd);
     } else {
-      dim3 grid(cdiv(L, 64), B * H);
-      hipLaunchKernelGGL((attn_fwd_dma_kernel<1>), grid, dim3(NT), 4 * TK * 128 * 2, s, qkv, lens, cu, out, lse, L,
-                         H, scale * kLog2e);
+      const int gx = cdiv(L, 64);
+      hipLaunchKernelGGL((attn_fwd_dma_kernel<1>), dim3(attn_map_grid(gx, BH)), dim3(NT), 4 * TK * 128 * 2, s, qkv,
+                         lens, cu, out, lse, L, H, scale * kLog2e, BH, gx, g_xcd);
     }
     return (int)hipGetLastError();
   }
@@ -1163,29 +1183,35 @@ SSAMD_API int ssamd_attn_bwd(const bf16_t* qkv, const int64_t* lens, const int64
   if ((long)B * L == 0 || rows == 0) return 0;
   hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv(rows * H * (D / 8), NT)), dim3(NT), 0, s, o, dO, delta, rows, H, D);
   if (D == 128) {  // fragments per wave of the two kernels: runtime-tunable (measured defaults)
+    const int BH = B * H;
     if (g_kv_dma) {
       constexpr size_t lds = 2 * (2 * TQ * 128 * 2 + 2 * TQ * 4);
       if (g_nf_kv == 1) {
+        const int gx = cdiv(L, 64);
         static const bool once1 = (allow_lds(attn_bwd_dkdv_dma_kernel<1, 2>, lds), true);
         (void)once1;
-        hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<1, 2>), dim3(cdiv(L, 64), B * H), dim3(NT), lds, s, qkv, lens,
-                           cu, dO, lse, delta, dqkv, L, H, scale * kLog2e, scale);
+        hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<1, 2>), dim3(attn_map_grid(gx, BH)), dim3(NT), lds, s, qkv, lens,
+                           cu, dO, lse, delta, dqkv, L, H, scale * kLog2e, scale, BH, gx, g_xcd);
       } else {
+        const int gx = cdiv(L, 128);
         static const bool once2 = (allow_lds(attn_bwd_dkdv_dma_kernel<2, 1>, lds), true);
         (void)once2;
-        hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<2, 1>), dim3(cdiv(L, 128), B * H), dim3(NT), lds, s, qkv, lens,
-                           cu, dO, lse, delta, dqkv, L, H, scale * kLog2e, scale);
+        hipLaunchKernelGGL((attn_bwd_dkdv_dma_kernel<2, 1>), dim3(attn_map_grid(gx, BH)), dim3(NT), lds, s, qkv, lens,
+                           cu, dO, lse, delta, dqkv, L, H, scale * kLog2e, scale, BH, gx, g_xcd);
       }
     } else if (g_nf_kv == 1) launch_dkdv<128, 1>(qkv, lens, cu, dO, lse, delta, dqkv, B, L, H, scale, s);
     else launch_dkdv<128, 2>(qkv, lens, cu, dO, lse, delta, dqkv, B, L, H, scale, s);
     if (g_q_dma) {
       constexpr size_t lds = 2 * 2 * TK * 128 * 2;  // 64 KiB
-      if (g_nf_q == 1)
-        hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<1, 2>), dim3(cdiv(L, 64), B * H), dim3(NT), lds, s, qkv, lens, cu,
-                           dO, lse, delta, dqkv, L, H, scale * kLog2e, scale);
-      else
-        hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<2, 2>), dim3(cdiv(L, 128), B * H), dim3(NT), lds, s, qkv, lens,
-                           cu, dO, lse, delta, dqkv, L, H, scale * kLog2e, scale);
+      if (g_nf_q == 1) {
+        const int gx = cdiv(L, 64);
+        hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<1, 2>), dim3(attn_map_grid(gx, BH)), dim3(NT), lds, s, qkv, lens,
+                           cu, dO, lse, delta, dqkv, L, H, scale * kLog2e, scale, BH, gx, g_xcd);
+      } else {
+        const int gx = cdiv(L, 128);
+        hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<2, 2>), dim3(attn_map_grid(gx, BH)), dim3(NT), lds, s, qkv, lens,
+                           cu, dO, lse, delta, dqkv, L, H, scale * kLog2e, scale, BH, gx, g_xcd);
+      }
     } else if (g_nf_q == 1) launch_dq<128, 1>(qkv, lens, cu, dO, lse, delta, dqkv, B, L, H, scale, s);
     else launch_dq<128, 2>(qkv, lens, cu, dO, lse, delta, dqkv, B, L, H, scale, s);
   } else {

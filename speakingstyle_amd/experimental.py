@@ -10,8 +10,8 @@ silently selecting a default (or an untested path).
 ``mi355x.experimental: {wgrad_first: "0"}`` in train.yaml does the same for ``train.py`` (the trainer
 calls ``configure`` with it; the environment wins on conflicts).
 
-Three switches select kernel-library variants (``KERNEL_SWITCHES``: ``gemm_stg``, ``gemm_mask_pre``,
-``gemm_bnh_stg``).
+Some switches select kernel-library variants (``KERNEL_SWITCHES``: ``gemm_stg``, ``gemm_mask_pre``,
+``gemm_bnh_stg``, ``attn_xcd``, ...).
 ``apply_kernel_switches()`` pushes their current values into the library; it runs when the library
 is first loaded (``ops/hip.py:lib``), after ``configure()`` and on entry to / exit from ``overrides``,
 so every path -- training, synthesis, kernel tests -- sees the same values.  The library's other
@@ -84,6 +84,7 @@ KNOBS: Dict[str, tuple] = {
     "gemm_ring_maxn": (256, int, "widest N of gemm_ring_maxk"),
     "gemm_skinny": (True, _bool, "small-M GEMMs on the skinny 16 x 16-tile kernel"),
     "gemm_skinny_maxm": (1024, int, "row limit of gemm_skinny"),
+    "attn_xcd": (True, _bool, "D=128 attention kernels keep all blocks of one (batch, head) sequence on one XCD"),
     "bn_fuse": (True, _bool, "PostNet BatchNorm backward started in the data-gradient GEMM's epilogue"),
     "defer_release": (False, _bool, "hand the side-stream weight-gradient inputs back to the trainer, freed "
                                     "during the next forward (holds a step's activations into it)"),
@@ -100,7 +101,7 @@ KNOBS: Dict[str, tuple] = {
 KERNEL_SWITCHES = {"gemm_stg": "ssamd_gemm_set_stg", "gemm_mask_pre": "ssamd_gemm_set_mask_pre",
                    "gemm_bnh_stg": "ssamd_gemm_set_bnh_stg", "gemm_ring_maxk": "ssamd_gemm_set_ring_maxk",
                    "gemm_ring_maxn": "ssamd_gemm_set_ring_maxn", "gemm_skinny": "ssamd_gemm_set_skinny",
-                   "gemm_skinny_maxm": "ssamd_gemm_set_skinny_maxm"}
+                   "gemm_skinny_maxm": "ssamd_gemm_set_skinny_maxm", "attn_xcd": "ssamd_attn_set_xcd"}
 
 _values: Dict[str, Any] = {}
 _parsed = [False]

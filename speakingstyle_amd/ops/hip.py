@@ -68,6 +68,7 @@ _SIGS = {
     "ssamd_attn_set_fwd": [I, I],
     "ssamd_attn_set_kv_dma": [I],
     "ssamd_attn_set_q_dma": [I, I],
+    "ssamd_attn_set_xcd": [I],
     "ssamd_wgrad_set_blocks": [I],
     "ssamd_wgrad_set_cus": [P, I],
     "ssamd_head_fwd": [P, P, P, P, L_, I, I, P, P],

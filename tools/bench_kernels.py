@@ -140,6 +140,12 @@ def main():
                 t2 = timeit(lambda: torch.autograd.grad(o, qh, g, retain_graph=True), args.iters)
                 row[f"bwd_ms_qdma{qd}_nf{nq}"] = round(t2, 3)
             hip.lib().ssamd_attn_set_q_dma(1, 2)
+            for xcd in (0, 1):  # plain block order / all blocks of a sequence on one XCD
+                hip.lib().ssamd_attn_set_xcd(xcd)
+                row[f"fwd_ms_xcd{xcd}"] = round(timeit(lambda: hip.attention(qh, lens, H), args.iters), 3)
+                t2 = timeit(lambda: torch.autograd.grad(o, qh, g, retain_graph=True), args.iters)
+                row[f"bwd_ms_xcd{xcd}"] = round(t2, 3)
+            hip.lib().ssamd_attn_set_xcd(1)
         if D == 32:  # query / key fragments per wave of the D = 32 kernels
             for nf in (1, 2, 4):
                 hip.lib().ssamd_attn_set_nf32(nf, nf)
