@@ -74,21 +74,40 @@ def get_mel_from_wav(audio: np.ndarray, stft: TacotronSTFT):
     return mel[0].numpy().astype(np.float32), energy[0].numpy().astype(np.float32)
 
 
-def griffin_lim(magnitudes: torch.Tensor, stft: TacotronSTFT, n_iters: int = 30) -> torch.Tensor:
-    angles = torch.exp(2j * np.pi * torch.rand_like(magnitudes))
-    spec = magnitudes * angles
+def griffin_lim(magnitudes: torch.Tensor, stft: TacotronSTFT, n_iters: int = 30, momentum: float = 0.0,
+                init_phase: torch.Tensor = None) -> torch.Tensor:
+    """magnitudes [B, n_fft/2+1, T] -> [B, hop * (T - 1)].  ``init_phase``: radians, shaped like the magnitudes
+    (default: uniform random); ``momentum``: 0 = the classic iteration, 0.99 = fast Griffin-Lim.  CUDA tensors
+    run the HIP kernels (``csrc/k_griffin.hip``), host tensors the torch.stft / torch.istft loop."""
+    from .. import ops
+
+    if init_phase is None:
+        init_phase = 2 * np.pi * torch.rand_like(magnitudes)
+    if magnitudes.is_cuda and ops.use_hip(magnitudes):
+        from ..ops import hip
+
+        return hip.griffin_lim(magnitudes.float().transpose(1, 2).contiguous(), stft.n_fft, stft.hop,
+                               stft.fft_window(magnitudes.device), n_iters, momentum,
+                               init_phase=init_phase.float().transpose(1, 2).contiguous())
+    spec = magnitudes * torch.exp(1j * init_phase)
     win = stft.window.to(magnitudes.device)
     y = torch.istft(spec, stft.n_fft, stft.hop, stft.win, window=win)
+    prev = None
     for _ in range(n_iters):
         s = torch.stft(y, stft.n_fft, stft.hop, stft.win, window=win, return_complex=True)
+        if momentum and prev is not None:
+            s, prev = s + momentum * (s - prev), s
+        else:
+            prev = s
         spec = magnitudes * torch.exp(1j * torch.angle(s))
         y = torch.istft(spec, stft.n_fft, stft.hop, stft.win, window=win)
     return y
 
 
-def inv_mel_spec(mel: torch.Tensor, stft: TacotronSTFT, n_iters: int = 30) -> torch.Tensor:
-    """log-mel [n_mel, T] -> waveform via pseudo-inverse mel basis + Griffin-Lim."""
+def inv_mel_spec(mel: torch.Tensor, stft: TacotronSTFT, n_iters: int = 30, momentum: float = 0.0,
+                 init_phase: torch.Tensor = None) -> torch.Tensor:
+    """log-mel [n_mel, T] -> waveform via pseudo-inverse mel basis + Griffin-Lim (``init_phase`` [n_fft/2+1, T])."""
     m = dynamic_range_decompression(mel)
     basis = stft.mel_basis.to(mel.device)
     mag = torch.clamp(torch.linalg.pinv(basis) @ m, min=0.0).unsqueeze(0)
-    return griffin_lim(mag, stft, n_iters)[0]
+    return griffin_lim(mag, stft, n_iters, momentum, None if init_phase is None else init_phase.unsqueeze(0))[0]

@@ -26,7 +26,7 @@ class Synthesizer:
         self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
         self.model = model if model is not None else get_model(restore_step, configs, self.device, train=False,
                                                                ignore_layers=tc.get("ignore_layers", []))
-        self.vocoder = vocoder if vocoder is not None else get_vocoder(mc, self.device)
+        self.vocoder = vocoder if vocoder is not None else get_vocoder(mc, self.device, preprocess_config=pp)
         pre = pp["preprocessing"]
         self.hop = pre["stft"]["hop_length"]
         self.sampling_rate = pre["audio"]["sampling_rate"]

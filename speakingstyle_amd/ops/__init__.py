@@ -392,3 +392,20 @@ def token_attention(q, K, V):
     qh = q.float().view(q.shape[0], NH, 1, D)
     w = torch.softmax(torch.matmul(qh, K.float().transpose(-1, -2).unsqueeze(0)) / (D ** 0.5), -1)
     return torch.matmul(w, V.float().unsqueeze(0)).reshape(q.shape[0], NH * D), w.squeeze(2)
+
+
+def istft(spec, n_fft, hop, window, lengths=None, width=None):
+    """Complex spectrum rows ([B, T, n_fft/2+1] padded, or [R, n_fft/2+1] packed with frame ``lengths``) -> wav
+    [B, W]: utterance b's hop * (T_b - 1) samples (torch.istft, centred), zeros after."""
+    if use_hip(spec):
+        return _hip().istft(spec, n_fft, hop, window, lengths, width)
+    return ref.istft(spec, n_fft, hop, window, lengths, width)
+
+
+def griffin_lim(x, n_fft, hop, window, n_iters, momentum=0.99, init_phase=None, seed=0, lengths=None,
+                int16_scale=None, mel_pinv=None, width=None, return_mag=False):
+    """Griffin-Lim phase reconstruction of magnitude rows (log-mel rows with ``mel_pinv``); see
+    ``ops.reference.griffin_lim``.  On the GPU one HIP launch per iteration (``csrc/k_griffin.hip``)."""
+    fn = _hip().griffin_lim if use_hip(x) else ref.griffin_lim
+    return fn(x, n_fft, hop, window, n_iters, momentum, init_phase, seed, lengths, int16_scale, mel_pinv, width,
+              return_mag)

@@ -2798,6 +2798,119 @@ def logmel(y, n_fft, hop, window, basis, clip=1e-5):
     return mel, energy
 
 
+# ------------------------------------------------------------------------ iSTFT / Griffin-Lim (csrc/k_griffin.hip)
+_SIGS.update({"ssamd_gl_init": [P, I, I, P, P, U64, P, I, I, P, P, P, P],
+              "ssamd_gl_iter": [P, P, P, P, F, I, P, P, I, I, I, P, P],
+              "ssamd_gl_final": [P, P, I, I, I, P, F, P, P, L_, P]})
+
+
+class GLPack:
+    """Row tables of a packed Griffin-Lim batch: ``rows`` int32 [R, 2] = {utterance, local frame} per frame row and
+    ``cu`` int32 [B + 1] = first row of every utterance, built from the host lengths and uploaded in one copy."""
+
+    def __init__(self, lens, device):
+        import numpy as np
+
+        lens = np.asarray([int(v) for v in lens], dtype=np.int64)
+        self.B, self.R = len(lens), int(lens.sum())
+        cu = np.zeros(self.B + 1, dtype=np.int64)
+        cu[1:] = np.cumsum(lens)
+        u = np.repeat(np.arange(self.B), lens)
+        rows = np.stack([u, np.arange(self.R) - cu[u]], axis=1)
+        assert self.R < 2 ** 31, "packed Griffin-Lim: too many rows"
+        self.max_len = int(lens.max()) if self.B else 0
+        host = torch.from_numpy(np.concatenate([cu, rows.reshape(-1)]).astype(np.int32))
+        self.buf = (host.pin_memory() if device.type == "cuda" else host).to(device, non_blocking=True)
+        self.cu, self.rows = self.buf[: self.B + 1], self.buf[self.B + 1:]
+
+
+def _gl_args(n_fft, hop, window):
+    _need(window, torch.float32, "griffin_lim.window")
+    if n_fft not in (512, 1024, 2048) or not 0 < hop <= n_fft or window.numel() != n_fft:
+        raise ValueError(f"griffin_lim: n_fft {n_fft} / hop {hop} / window {tuple(window.shape)} not covered by the "
+                         "kernels (n_fft 512, 1024 or 2048, hop <= n_fft, an [n_fft] window)")
+
+
+def _gl_pack(lens, device, n_fft, hop):
+    pack = GLPack(lens, device)
+    if 2 * hop * pack.max_len + n_fft >= 2 ** 31 - 1:  # csrc/gl_frames.h gl_fits_int: positions are 32-bit
+        raise ValueError(f"griffin_lim: an utterance of {pack.max_len} frames exceeds the kernels' 32-bit positions")
+    return pack
+
+
+def _gl_final(frame, pack, n_fft, hop, window, width, lens, int16_scale):
+    W = int(width) if width is not None else max([hop * (n - 1) for n in lens] + [0])
+    out = torch.empty(pack.B, W, device=frame.device, dtype=torch.float32 if int16_scale is None else torch.int16)
+    f32 = int16_scale is None
+    rc = lib().ssamd_gl_final(_ptr(frame), _ptr(pack.cu), pack.B, n_fft, hop, _ptr(window),
+                              1.0 if f32 else float(int16_scale), _ptr(out) if f32 else None,
+                              None if f32 else _ptr(out), W, _stream())
+    _check(rc, "ssamd_gl_final")
+    return out
+
+
+def istft(spec, n_fft, hop, window, lengths=None, width=None):
+    """Complex spectrum rows -- padded [B, T, n_fft/2+1] (+ optional frame ``lengths``) or packed [R, n_fft/2+1]
+    with ``lengths`` -- -> wav [B, W] fp32 (torch.istft, centred): utterance b's hop * (T_b - 1) samples, zeros
+    after.  ``window``: the [n_fft] window (``TacotronSTFT.fft_window``)."""
+    _gl_args(n_fft, hop, window)
+    rows, lens = ref.gl_rows(spec, lengths)
+    if rows.dtype != torch.complex64:
+        raise TypeError(f"istft.spec: expected complex64, got {rows.dtype}")
+    NB = n_fft // 2 + 1
+    assert rows.shape[1] == NB
+    x = torch.view_as_real(rows.contiguous())
+    pack = _gl_pack(lens, rows.device, n_fft, hop)
+    frame = torch.empty(pack.R, n_fft, device=rows.device, dtype=torch.float32)
+    rc = lib().ssamd_gl_init(_ptr(x), 2, 0, None, None, 0, _ptr(pack.rows), pack.R, n_fft, _ptr(window), None,
+                             _ptr(frame), _stream())
+    _check(rc, "ssamd_gl_init")
+    return _gl_final(frame, pack, n_fft, hop, window, width, lens, None)
+
+
+def griffin_lim(x, n_fft, hop, window, n_iters, momentum=0.99, init_phase=None, seed=0, lengths=None,
+                int16_scale=None, mel_pinv=None, width=None, return_mag=False):
+    """``ops.reference.griffin_lim`` on the GPU (fp32): magnitude rows, or log-mel rows with ``mel_pinv``
+    [n_fft/2+1, n_mel], padded [B, T, C] (+ ``lengths``) or packed [R, C] with ``lengths``.  One ``gl_init`` launch,
+    one ``gl_iter`` launch per iteration (two frame buffers, ping-pong), one ``gl_final``; every utterance comes out
+    bitwise as if alone.  -> wav [B, W] fp32, or int16 (``* int16_scale``, clamped) written by the kernel."""
+    _gl_args(n_fft, hop, window)
+    rows, lens = ref.gl_rows(x, lengths)
+    rows = rows.contiguous()
+    _need(rows, torch.float32, "griffin_lim.x")
+    NB = n_fft // 2 + 1
+    dev = rows.device
+    if mel_pinv is not None:
+        _need(mel_pinv, torch.float32, "griffin_lim.mel_pinv")
+        assert mel_pinv.shape == (NB, rows.shape[1]) and rows.shape[1] <= n_fft, "griffin_lim: mel_pinv is [NB, n_mel]"
+    else:
+        assert rows.shape[1] == NB, "griffin_lim: rows are not [*, n_fft/2+1] magnitudes (mel_pinv missing?)"
+    ph = None
+    if init_phase is not None:
+        ph = ref.gl_rows(init_phase, lengths)[0].contiguous()
+        _need(ph, torch.float32, "griffin_lim.init_phase")
+        assert ph.shape == (rows.shape[0], NB)
+    pack = _gl_pack(lens, dev, n_fft, hop)
+    R = pack.R
+    mag = torch.empty(R, NB, device=dev, dtype=torch.float32)
+    fa = torch.empty(R, n_fft, device=dev, dtype=torch.float32)
+    L, s = lib(), _stream()
+    rc = L.ssamd_gl_init(_ptr(rows), 1 if mel_pinv is not None else 0, rows.shape[1], _ptr(mel_pinv), _ptr(ph),
+                         int(seed) & 0xFFFFFFFF, _ptr(pack.rows), R, n_fft, _ptr(window), _ptr(mag), _ptr(fa), s)
+    _check(rc, "ssamd_gl_init")
+    n_iters = int(n_iters)
+    if n_iters > 0 and R > 0:
+        fb = torch.empty_like(fa)
+        cprev = torch.empty(R, NB, 2, device=dev, dtype=torch.float32) if momentum != 0 else None
+        for it in range(n_iters):
+            rc = L.ssamd_gl_iter(_ptr(fa), _ptr(fb), _ptr(mag), _ptr(cprev), float(momentum), 1 if it == 0 else 0,
+                                 _ptr(pack.rows), _ptr(pack.cu), R, n_fft, hop, _ptr(window), s)
+            _check(rc, "ssamd_gl_iter")
+            fa, fb = fb, fa
+    out = _gl_final(fa, pack, n_fft, hop, window, width, lens, int16_scale)
+    return (out, mag) if return_mag else out
+
+
 # ------------------------------------------------------------------------ N = 1 heads
 class _HeadFn(torch.autograd.Function):
     """Variance-predictor head Linear(C -> 1) + pad mask (one wave per row)."""

@@ -173,3 +173,107 @@ def fastspeech2_loss_terms(
     logd_t = torch.log(d_target.float() + 1.0)
     dur_l = masked_mean_mse(logd_pred, logd_t, src_valid.float())
     return mel_l, post_l, pitch_l, energy_l, dur_l
+
+
+# ------------------------------------------------------------------ iSTFT / Griffin-Lim (audio/stft.py semantics)
+def gl_min_frames(n_fft: int, hop: int) -> int:
+    """Fewest frames at which reflect padding is defined (hop * (T - 1) > n_fft / 2); csrc/gl_frames.h."""
+    return n_fft // (2 * hop) + 2
+
+
+def gl_rows(x, lengths=None):
+    """Frame rows of a batch -> (packed rows [R, C], host frame counts).  ``x``: padded ``[B, T, C]`` (``lengths``
+    optional, clipped to T), packed ``[R, C]`` rows with ``lengths``, or one utterance ``[T, C]`` without."""
+    if x.dim() == 2:
+        lens = [x.shape[0]] if lengths is None else [max(0, int(v)) for v in lengths]
+        assert sum(lens) == x.shape[0], "packed rows vs lengths"
+        return x, lens
+    assert x.dim() == 3, "frame rows: [B, T, C] or [R, C]"
+    B, T, _ = x.shape
+    lens = [T] * B if lengths is None else [max(0, min(int(v), T)) for v in lengths]
+    if all(n == T for n in lens):
+        return x.reshape(B * T, x.shape[2]), lens
+    return torch.cat([x[b, :n] for b, n in enumerate(lens)], 0), lens
+
+
+def _hash_u32(x):
+    """csrc/common.h hash_u32 on int64 tensors holding uint32 values."""
+    m = 0xFFFFFFFF
+    x = x ^ (x >> 16)
+    x = (x * 0x7FEB352D) & m
+    x = x ^ (x >> 15)
+    x = (x * 0x846CA68B) & m
+    return x ^ (x >> 16)
+
+
+def gl_seed_phase(seed: int, T: int, NB: int, device=None, dtype=torch.float32):
+    """The kernels' seeded initial phase of one utterance: 2 pi * hash(seed, local frame, bin) / 2^32 -> [T, NB]."""
+    f = torch.arange(T, dtype=torch.int64, device=device).unsqueeze(1)
+    k = torch.arange(NB, dtype=torch.int64, device=device).unsqueeze(0)
+    h = _hash_u32(_hash_u32((int(seed) & 0xFFFFFFFF) ^ ((f * 0x9E3779B9) & 0xFFFFFFFF)) ^ k)
+    return (h.to(torch.float32) * (2.0 / 4294967296.0)).to(dtype) * math.pi
+
+
+def _istft_one(spec, n_fft, hop, window):
+    """spec [T, NB] complex -> hop * (T - 1) samples (torch.istft, centred)."""
+    if spec.shape[0] <= 1:
+        return torch.zeros(0, dtype=window.dtype, device=spec.device)
+    return torch.istft(spec.transpose(0, 1).unsqueeze(0), n_fft, hop, n_fft, window=window, center=True)[0]
+
+
+def _wav_batch(wavs, width, int16_scale, dtype, device):
+    W = int(width) if width is not None else max([w.shape[0] for w in wavs] + [0])
+    out = torch.zeros(len(wavs), W, dtype=dtype, device=device)
+    for b, w in enumerate(wavs):
+        n = min(W, w.shape[0])
+        out[b, :n] = w[:n]
+    if int16_scale is not None:
+        out = (out * int16_scale).clamp(-32768, 32767).to(torch.int16)
+    return out
+
+
+def istft(spec, n_fft, hop, window, lengths=None, width=None):
+    """Complex spectrum rows (``gl_rows`` layouts, C = n_fft/2 + 1) -> wav [B, W]: utterance b's hop * (T_b - 1)
+    samples, zeros after (W = ``width`` or the longest).  ``window``: the [n_fft] analysis window."""
+    rows, lens = gl_rows(spec, lengths)
+    window = window.to(rows.real.dtype)
+    wavs, o = [], 0
+    for n in lens:
+        wavs.append(_istft_one(rows[o:o + n], n_fft, hop, window))
+        o += n
+    return _wav_batch(wavs, width, None, window.dtype, rows.device)
+
+
+def griffin_lim(x, n_fft, hop, window, n_iters, momentum=0.99, init_phase=None, seed=0, lengths=None,
+                int16_scale=None, mel_pinv=None, width=None, return_mag=False):
+    """Griffin-Lim on magnitude rows, or log-mel rows when ``mel_pinv`` [n_fft/2+1, n_mel] is given
+    (mag = clamp(pinv @ exp(mel), 0)); row layouts as ``gl_rows``.  Every utterance on its own:
+    S = mag * exp(i phase) -> y = istft(S); per iteration c = stft(y), t = c + momentum * (c - c_prev)
+    (t = c on the first), S = mag * t / |t| (mag where t = 0), y = istft(S).  ``momentum = 0`` is the classic
+    algorithm, 0.99 the fast variant.  Utterances below ``gl_min_frames`` get no iteration.  ``init_phase``:
+    radians in x's layout, else ``gl_seed_phase(seed)``.  Computes in x's dtype (float64 = the oracle).
+    -> wav [B, W] (int16 = (wav * int16_scale).clamp.to(int16)); with ``return_mag`` also the packed mag rows."""
+    rows, lens = gl_rows(x, lengths)
+    window = window.to(rows.dtype)
+    mag = torch.clamp(torch.exp(rows) @ mel_pinv.to(rows.dtype).t(), min=0.0) if mel_pinv is not None else rows
+    NB = n_fft // 2 + 1
+    assert mag.shape[1] == NB, "griffin_lim: rows are not [*, n_fft/2+1] magnitudes (mel_pinv missing?)"
+    ph_rows = None if init_phase is None else gl_rows(init_phase, lengths)[0].to(rows.dtype)
+    wavs, o = [], 0
+    for n in lens:
+        m = mag[o:o + n]
+        ph = ph_rows[o:o + n] if ph_rows is not None else gl_seed_phase(seed, n, NB, rows.device, rows.dtype)
+        o += n
+        y = _istft_one(torch.polar(m, ph), n_fft, hop, window)
+        prev = None
+        for _ in range(n_iters if n >= gl_min_frames(n_fft, hop) else 0):
+            c = torch.stft(y.unsqueeze(0), n_fft, hop, n_fft, window=window, center=True, pad_mode="reflect",
+                           return_complex=True)[0].transpose(0, 1)
+            t = c if (prev is None or momentum == 0) else c + momentum * (c - prev)
+            prev = c
+            a = t.abs()
+            s = torch.where(a > 0, m * (t / torch.where(a > 0, a, torch.ones_like(a))), m.to(t.dtype))
+            y = _istft_one(s, n_fft, hop, window)
+        wavs.append(y)
+    out = _wav_batch(wavs, width, int16_scale, rows.dtype, rows.device)
+    return (out, mag) if return_mag else out

@@ -134,7 +134,7 @@ def train(args, configs):
 
     vocoder = None
     if rank == 0 and not getattr(args, "no_vocoder", False):
-        vocoder = mutil.get_vocoder(model_config, device)
+        vocoder = mutil.get_vocoder(model_config, device, preprocess_config=preprocess_config)
 
     paths = train_config["path"]
     train_log_path = os.path.join(paths["log_path"], "train")

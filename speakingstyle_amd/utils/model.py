@@ -113,13 +113,25 @@ def vocoder_config(path: Optional[str] = None) -> AttrDict:
     return default_config()
 
 
-def get_vocoder(model_config, device, ckpt_dir: Optional[str] = None, allow_random: bool = True):
+def get_vocoder(model_config, device, ckpt_dir: Optional[str] = None, allow_random: bool = True,
+                preprocess_config=None):
     """HiFi-GAN generator; loads ``generator_{LJSpeech,universal}.pth.tar`` when
     present (weights_only), otherwise random init (benchmarks).  MelGAN via
-    torch.hub is not supported (network download)."""
+    torch.hub is not supported (network download).
+
+    ``vocoder.model: "GriffinLim"`` builds the checkpoint-free ``models.griffinlim.GriffinLim`` (optional
+    ``vocoder.n_iters`` / ``vocoder.momentum``) for the STFT / mel settings of ``preprocess_config`` (default: the
+    preprocessing defaults, 22.05 kHz / 1024 / 256 / 80 mels)."""
     name = model_config["vocoder"]["model"]
+    if name == "GriffinLim":
+        from ..config import normalize_preprocess_config
+        from ..models.griffinlim import GriffinLim
+
+        voc = model_config["vocoder"]
+        pp = preprocess_config if preprocess_config is not None else normalize_preprocess_config(None)
+        return GriffinLim(pp, n_iters=int(voc.get("n_iters", 60)), momentum=float(voc.get("momentum", 0.99)))
     if name != "HiFi-GAN":
-        raise ValueError(f"vocoder {name!r} not supported (HiFi-GAN only)")
+        raise ValueError(f"vocoder {name!r} not supported (HiFi-GAN, GriffinLim)")
     speaker = model_config["vocoder"]["speaker"]
     gen = Generator(vocoder_config())
     ckpt_dir = ckpt_dir or os.path.join(ROOT, "hifigan")
@@ -141,7 +153,8 @@ def vocoder_infer(mels, vocoder, model_config, preprocess_config, lengths=None, 
     x = mels if channel_last else mels.transpose(1, 2)
     mx = preprocess_config["preprocessing"]["audio"]["max_wav_value"]
     if x.is_cuda:
-        x = x.to(torch.bfloat16).contiguous()
+        # the generator's kernels take bf16; a vocoder without a generator (GriffinLim) consumes the mel in fp32
+        x = x.to(getattr(vocoder, "mel_dtype", torch.bfloat16)).contiguous()
         hop = preprocess_config["preprocessing"]["stft"]["hop_length"]
         frames = None if lengths is None else [-(-int(n) // hop) for n in lengths]
         # int16 written by the conv_post kernel; length-bucketed when the lengths are known

@@ -90,6 +90,30 @@ def from_mels(input_mels_dir: str, output_dir: str, checkpoint_file: str, device
     return _write(names, vocode(g, h, mels, device, batch_size), output_dir, "_generated_e2e", h)
 
 
+def from_mels_griffin_lim(input_mels_dir: str, output_dir: str, preprocess_config=None, device=None,
+                          batch_size: int = 16, n_iters: int = 60, momentum: float = 0.99) -> List[str]:
+    """``from_mels`` with no checkpoint: every ``.npy`` log-mel through ``models.griffinlim.GriffinLim`` (the STFT /
+    mel settings of ``preprocess_config``, default the preprocessing defaults) -> ``{name}_generated_e2e.wav``."""
+    from ..config import normalize_preprocess_config
+    from ..models.griffinlim import GriffinLim
+
+    device = device or torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    pp = preprocess_config if preprocess_config is not None else normalize_preprocess_config(None)
+    voc = GriffinLim(pp, n_iters=n_iters, momentum=momentum)
+    names = _listdir(input_mels_dir, ".npy")
+    wavs: List[np.ndarray] = []
+    for s in range(0, len(names), batch_size):
+        mels = []
+        for n in names[s:s + batch_size]:
+            m = torch.from_numpy(np.load(os.path.join(input_mels_dir, n), allow_pickle=False)).float()
+            mels.append(m.reshape(-1, m.shape[-1]).t())  # [T, n_mel] rows
+        lens = [m.shape[0] for m in mels]
+        pcm = voc.infer_packed(torch.cat(mels, 0).to(device), lens, int16_scale=32768.0).cpu().numpy()
+        wavs.extend(pcm[k, : n * voc.hop] for k, n in enumerate(lens))
+    h = H.AttrDict(sampling_rate=pp["preprocessing"]["audio"]["sampling_rate"])
+    return _write(names, wavs, output_dir, "_generated_e2e", h)
+
+
 def _write(names, wavs, output_dir, suffix, h) -> List[str]:
     os.makedirs(output_dir, exist_ok=True)
     paths = []

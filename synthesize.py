@@ -6,6 +6,7 @@ prosody control and GST style weights.
   batch:   python synthesize.py --mode batch --source val.txt --restore_step N -p -m -t
   word-level control: --word_pitch 1,1.3,0.8 --word_energy ... --word_duration ... (one factor per word)
   GST:     --style_weights 0.5,0,0,...   (one weight per style token)
+  Griffin-Lim instead of HiFi-GAN (no vocoder checkpoint): --vocoder griffin_lim   (all modes)
   serve:   python synthesize.py --mode serve [--source lines.txt] --restore_step N -p -m -t
            one text per line (from --source or stdin) -> {result_path}/serve_{line:04d}.wav, through the serving
            entry (infer/serve.py: bucketed HIP graphs on the GPU); prints the graph statistics at the end
@@ -31,12 +32,19 @@ def _floats(s):
     return None if s is None else [float(x) for x in s.split(",") if x.strip()]
 
 
+def _choose_vocoder(model_config, choice):
+    """--vocoder griffin_lim: the checkpoint-free Griffin-Lim vocoder instead of the model config's."""
+    if choice == "griffin_lim":
+        model_config["vocoder"] = dict(model_config["vocoder"], model="GriffinLim")
+
+
 def serve(args):
     """One wav per input line through ``infer.serve.Synthesizer``."""
     from speakingstyle_amd.audio.io import write_wav
     from speakingstyle_amd.infer.serve import Synthesizer
 
     configs = load_configs(args.preprocess_config, args.model_config, args.train_config)
+    _choose_vocoder(configs[1], args.vocoder)
     tts = Synthesizer(configs, args.restore_step)
     result_path = args.result_path or configs[2]["path"]["result_path"]
     os.makedirs(result_path, exist_ok=True)
@@ -78,6 +86,8 @@ def main(argv=None):
     ap.add_argument("--batch_size", type=int, default=8)
     ap.add_argument("--plot", action="store_true", help="also write mel/pitch/energy PNGs")
     ap.add_argument("--result_path", type=str, default=None)
+    ap.add_argument("--vocoder", type=str, choices=["config", "griffin_lim"], default="config",
+                    help="config: the model config's vocoder (HiFi-GAN); griffin_lim: no checkpoint needed")
     args = ap.parse_args(argv)
     if args.mode == "serve":
         assert args.text is None
@@ -91,7 +101,8 @@ def main(argv=None):
     pp, mc, tc = configs
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model = get_model(args.restore_step, configs, device, train=False, ignore_layers=tc.get("ignore_layers", []))
-    vocoder = get_vocoder(mc, device)
+    _choose_vocoder(mc, args.vocoder)
+    vocoder = get_vocoder(mc, device, preprocess_config=pp)
     result_path = args.result_path or tc["path"]["result_path"]
     os.makedirs(result_path, exist_ok=True)
     controls = [args.pitch_control, args.energy_control, args.duration_control]

@@ -31,12 +31,89 @@ def timeit(fn, iters):
     return s.elapsed_time(e) / iters  # ms
 
 
+def bench_griffin_lim(out_path, rounds=7, n_iters=60):
+    """60 Griffin-Lim iterations: the HIP kernels (csrc/k_griffin.hip, one launch per iteration, packed batch)
+    against the torch.stft / torch.istft loop of ``audio/stft.py`` (padded batch) on the same GPU.  The two
+    alternate in one process, each call timed with device events; the table reports the median and the spread."""
+    import numpy as np
+
+    from speakingstyle_amd import ops
+    from speakingstyle_amd.audio.stft import TacotronSTFT, griffin_lim
+
+    dev = torch.device("cuda")
+    stft = TacotronSTFT().to(dev)
+    win = stft.fft_window(dev)
+    rng = np.random.default_rng(0)
+    workloads = [("1 utterance x 800 frames", [800]),
+                 ("16 utterances, 300-850 frames", [int(v) for v in rng.integers(300, 851, size=16)])]
+
+    def timed(fn):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        torch.cuda.synchronize()
+        return s.elapsed_time(e)
+
+    lines = [f"Griffin-Lim, {n_iters} iterations, n_fft 1024 / hop 256, fp32, {torch.cuda.get_device_name(0)}",
+             f"{rounds} alternating rounds per arm after 2 warm-up rounds; device-event time per call (ms)", "",
+             f"{'workload':32s} {'momentum':>8s} {'arm':>22s} {'median':>9s} {'min':>9s} {'max':>9s} {'us/iter':>9s}"]
+    for name, lens in workloads:
+        B, Tm = len(lens), max(lens)
+        g = torch.Generator(device="cpu").manual_seed(1)
+        y = (0.5 * torch.sin(2 * math.pi * 220 * torch.arange(256 * (Tm - 1)) / 22050.0)
+             + 0.1 * torch.randn(B, 256 * (Tm - 1), generator=g)).clamp(-1, 1).to(dev)
+        mag = stft.magnitudes(y)  # [B, 513, Tm]
+        for b, n in enumerate(lens):
+            mag[b, :, n:] = 0
+        ph = 2 * math.pi * torch.rand(mag.shape, generator=g).to(dev)
+        rows = torch.cat([mag[b, :, :n].t() for b, n in enumerate(lens)], 0).contiguous()
+        ph_rows = torch.cat([ph[b, :, :n].t() for b, n in enumerate(lens)], 0).contiguous()
+        for momentum in (0.0, 0.99):
+            def run_hip():
+                return hip.griffin_lim(rows, 1024, 256, win, n_iters, momentum, init_phase=ph_rows, lengths=lens)
+
+            def run_torch():
+                ops.set_backend("reference")  # the torch loop on the GPU tensors
+                try:
+                    return griffin_lim(mag, stft, n_iters, momentum, init_phase=ph)
+                finally:
+                    ops.set_backend(None)
+
+            t = {"hip packed (1 launch/iter)": [], "torch.stft/istft loop": []}
+            for r in range(rounds + 2):
+                for arm, fn in (("hip packed (1 launch/iter)", run_hip), ("torch.stft/istft loop", run_torch)):
+                    ms = timed(fn)
+                    if r >= 2:
+                        t[arm].append(ms)
+            for arm, v in t.items():
+                v.sort()
+                med = v[len(v) // 2]
+                lines.append(f"{name:32s} {momentum:8.2f} {arm:>22s} {med:9.3f} {v[0]:9.3f} {v[-1]:9.3f} "
+                             f"{1e3 * med / n_iters:9.1f}")
+            a, b = t["hip packed (1 launch/iter)"], t["torch.stft/istft loop"]
+            lines.append(f"{'':32s} {'':8s} {'torch / hip (medians)':>22s} {b[len(b) // 2] / a[len(a) // 2]:9.2f}")
+        lines.append(f"{'':32s} frames: {sum(lens)} packed, {B * Tm} padded")
+    text = "\n".join(lines) + "\n"
+    print(text, end="", flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=160000)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--only-attn", action="store_true")
+    ap.add_argument("--griffin-lim", action="store_true",
+                    help="only the Griffin-Lim arm: HIP kernels vs the torch loop, table written to --out")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                  "profiles", "griffin_lim.txt"))
     args = ap.parse_args()
+    if args.griffin_lim:
+        return bench_griffin_lim(args.out)
     dev = "cuda"
     B = 200
     L = args.rows // B
