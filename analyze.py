@@ -6,6 +6,9 @@
         [--pitch_control 1.2 --energy_control 1 --duration_control 1] [--outlier_k 3]
   one-batch forward / style-encoder inspection (notebooks/ref_encoder.ipynb):
     python analyze.py inspect --restore_step 0 -p P -m M -t T [--synthetic]
+  objective metrics of free-running synthesis against the recordings (MCD, F0 / energy error along a DTW path):
+    python analyze.py objective --restore_step 900000 -p P -m M -t T [--source val.txt] [--out_dir analysis]
+        [--pitch_control 1 --energy_control 1 --duration_control 1] [--n_ceps 13] [--batch_size 32] [--cpu]
 """
 import argparse
 import json
@@ -17,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("command", choices=["variance", "inspect"])
+    ap.add_argument("command", choices=["variance", "inspect", "objective"])
     ap.add_argument("--restore_step", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1234, help="parameter init seed (restore_step 0: reproducible runs)")
     ap.add_argument("-p", "--preprocess_config", required=True)
@@ -29,7 +32,8 @@ def main(argv=None):
     ap.add_argument("--energy_control", type=float, default=1.0)
     ap.add_argument("--duration_control", type=float, default=1.0)
     ap.add_argument("--outlier_k", type=float, default=3.0)
-    ap.add_argument("--batch_size", type=int, default=8)
+    ap.add_argument("--batch_size", type=int, default=None, help="default: 8 (variance), 32 (objective)")
+    ap.add_argument("--n_ceps", type=int, default=13, help="objective: mel cepstra 1 .. n_ceps enter the MCD")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--cpu", action="store_true")
     a = ap.parse_args(argv)
@@ -48,7 +52,13 @@ def main(argv=None):
 
         src = a.source or os.path.join(configs[0]["path"]["preprocessed_path"], "val.txt")
         rep = analyze(model, configs, src, dev, (a.pitch_control, a.energy_control, a.duration_control), a.out_dir,
-                      a.batch_size, a.outlier_k)
+                      a.batch_size or 8, a.outlier_k)
+    elif a.command == "objective":
+        from speakingstyle_amd.analysis.objective import evaluate_objective
+
+        src = a.source or os.path.join(configs[0]["path"]["preprocessed_path"], "val.txt")
+        rep = evaluate_objective(model, configs, src, dev, (a.pitch_control, a.energy_control, a.duration_control),
+                                 a.batch_size or 32, a.out_dir, a.n_ceps)
     else:
         from speakingstyle_amd.analysis.inspect import inspect_batch
 

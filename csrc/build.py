@@ -140,6 +140,18 @@ def build_gl_selftest():
     return exe
 
 
+def build_dtw_selftest():
+    """The DTW direction-plane index arithmetic (csrc/dtw_index.h) as plain host code under ASan+UBSan: returns the
+    self-test executable (csrc/selftest_dtw_index.cpp) in build/sanitize/."""
+    out_dir = os.path.join(ROOT, "build", "sanitize")
+    os.makedirs(out_dir, exist_ok=True)
+    test = os.path.join(HERE, "selftest_dtw_index.cpp")
+    exe = os.path.join(out_dir, "selftest_dtw_index")
+    if _stale(exe, [test, os.path.join(HERE, "dtw_index.h")]):
+        _run(["g++", "-O1", "-g", "-std=c++17", "-I", HERE] + SANITIZERS["asan"] + ["-o", exe, test])
+    return exe
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 4))

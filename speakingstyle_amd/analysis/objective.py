@@ -1,0 +1,227 @@
+"""Objective synthesis metrics: how far is a free-running synthesis from the recording of the same utterance?
+
+The synthesized and the recorded utterance differ in length, so every per-utterance figure is taken along a dynamic
+time warping path between their mel cepstra (``ops.dtw``: one HIP workgroup per pair on the GPU, the torch
+wavefront of ``ops.reference`` on the CPU):
+
+  mcd_db          mel-cepstral distortion, (10 sqrt(2) / ln 10) * DTW cost / path length, over cepstra 1..n_ceps
+                  of the stored natural-log mel (orthonormal DCT-II, c0 dropped)
+  logmel_l1       mean |log-mel difference| along the path, all mel channels
+  pitch_rmse      RMSE of the frame-level pitch / energy contours gathered along the path (de-normalised with
+  energy_rmse     ``stats.json``; phoneme-level features are expanded to frames with the predicted / stored durations)
+  pitch_corr      Pearson correlation of the two pitch contours along the path (nan when one is constant)
+  dur_mae_frames  mean |predicted - stored| phoneme duration in frames (no alignment involved)
+  len_ratio       synthesized frames / recorded frames
+
+The x side of every alignment is the synthesis, the y side the recording.  A synthesis of zero frames has no
+alignment: its path metrics are nan, it is counted in ``n_empty`` and left out of the means and medians.
+"""
+from __future__ import annotations
+
+import csv
+import json
+import math
+import os
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .. import ops
+from .variance import _stats
+
+MCD_SCALE = 10.0 * math.sqrt(2.0) / math.log(10.0)
+METRICS = ("mcd_db", "logmel_l1", "pitch_rmse", "energy_rmse", "pitch_corr", "dur_mae_frames", "len_ratio")
+
+
+def dct_matrix(n_mel: int, n_ceps: int, device=None, dtype=torch.float32) -> torch.Tensor:
+    """[n_mel, n_ceps]: columns k = 1 .. n_ceps of the orthonormal DCT-II, sqrt(2/N) cos(pi (n + 1/2) k / N)."""
+    if not 1 <= n_ceps < n_mel:
+        raise ValueError(f"n_ceps {n_ceps} must lie in 1 .. n_mel - 1 = {n_mel - 1}")
+    n = torch.arange(n_mel, dtype=torch.float64).unsqueeze(1)
+    k = torch.arange(1, n_ceps + 1, dtype=torch.float64).unsqueeze(0)
+    return (math.sqrt(2.0 / n_mel) * torch.cos(math.pi / n_mel * (n + 0.5) * k)).to(device=device, dtype=dtype)
+
+
+def mel_cepstra(logmel: torch.Tensor, n_ceps: int = 13) -> torch.Tensor:
+    """Natural-log mel rows [..., n_mel] -> mel cepstra 1 .. n_ceps [..., n_ceps] (fp32, or float64 for float64 rows):
+    one small full-precision matmul."""
+    x = logmel if logmel.dtype == torch.float64 else logmel.float()
+    return x @ dct_matrix(x.shape[-1], n_ceps, x.device, x.dtype)
+
+
+def align(pred_mel, pred_lens, true_mel, true_lens, n_ceps: int = 13):
+    """DTW of packed log-mel rows [R, n_mel] on their cepstra -> ``ops.dtw``'s (cost [P], path [P, Lmax, 2], path_len
+    [P]); path[..., 0] indexes the synthesized frames, path[..., 1] the recorded ones."""
+    return ops.dtw(mel_cepstra(pred_mel, n_ceps).contiguous(), mel_cepstra(true_mel, n_ceps).contiguous(),
+                   list(pred_lens), list(true_lens))
+
+
+def _starts(lens, device):
+    cu = np.zeros(len(lens), dtype=np.int64)
+    cu[1:] = np.cumsum(lens)[:-1]
+    return torch.from_numpy(cu).to(device)
+
+
+def _along(path, plen, pred_lens, true_lens):
+    """Global row indices of the path cells in the packed pred / true rows and the mask of real cells."""
+    dev = path.device
+    mask = torch.arange(path.shape[1], device=dev).unsqueeze(0) < plen.unsqueeze(1)
+    ip = (path[..., 0].long() + _starts(pred_lens, dev).unsqueeze(1)).masked_fill(~mask, 0)
+    it = (path[..., 1].long() + _starts(true_lens, dev).unsqueeze(1)).masked_fill(~mask, 0)
+    return ip, it, mask
+
+
+def _rmse(a, b, mask, n):
+    d = (a - b).masked_fill(~mask, 0.0)
+    return torch.sqrt((d * d).sum(1) / n)
+
+
+def _pearson(a, b, mask, n):
+    a, b = a.masked_fill(~mask, 0.0), b.masked_fill(~mask, 0.0)
+    da = (a - (a.sum(1) / n).unsqueeze(1)).masked_fill(~mask, 0.0)
+    db = (b - (b.sum(1) / n).unsqueeze(1)).masked_fill(~mask, 0.0)
+    den = torch.sqrt((da * da).sum(1) * (db * db).sum(1))
+    return torch.where(den > 0, (da * db).sum(1) / den, torch.full_like(den, float("nan")))
+
+
+def utterance_metrics(pred_mel, pred_lens, true_mel, true_lens, pred_pitch=None, true_pitch=None, pred_energy=None,
+                      true_energy=None, pred_dur: Optional[Sequence] = None, true_dur: Optional[Sequence] = None,
+                      n_ceps: int = 13) -> Dict[str, np.ndarray]:
+    """Per-pair metrics of P utterances.  ``pred_mel`` [Rp, n_mel] / ``true_mel`` [Rt, n_mel]: packed log-mel rows with
+    host frame counts ``pred_lens`` / ``true_lens``; ``*_pitch`` / ``*_energy``: packed frame-level contours [Rp] / [Rt]
+    in physical units; ``*_dur``: one integer array of phoneme durations per utterance.  -> {metric: float64 [P]} plus
+    ``path_len`` (int) and ``path`` / the DTW ``cost`` as returned by ``align``.  Metrics whose inputs are missing are
+    left out."""
+    pred_lens, true_lens = [int(v) for v in pred_lens], [int(v) for v in true_lens]
+    cost, path, plen = align(pred_mel, pred_lens, true_mel, true_lens, n_ceps)
+    ip, it, mask = _along(path, plen, pred_lens, true_lens)
+    n = plen.double()
+    out = {"mcd_db": MCD_SCALE * cost.double() / n}
+    dm = (pred_mel.double()[ip] - true_mel.double()[it]).abs().sum(-1).masked_fill(~mask, 0.0)
+    out["logmel_l1"] = dm.sum(1) / (n * pred_mel.shape[1])
+    if pred_pitch is not None and true_pitch is not None:
+        a, b = pred_pitch.double()[ip], true_pitch.double()[it]
+        out["pitch_rmse"] = _rmse(a, b, mask, n)
+        out["pitch_corr"] = _pearson(a, b, mask, n)
+    if pred_energy is not None and true_energy is not None:
+        out["energy_rmse"] = _rmse(pred_energy.double()[ip], true_energy.double()[it], mask, n)
+    res = {k: v.cpu().numpy() for k, v in out.items()}
+    if pred_dur is not None and true_dur is not None:
+        res["dur_mae_frames"] = np.asarray([np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).mean()
+                                            for a, b in zip(pred_dur, true_dur)])
+    res["len_ratio"] = np.asarray(pred_lens, np.float64) / np.asarray(true_lens, np.float64)
+    res["path_len"] = plen.cpu().numpy()
+    res["cost"] = cost.cpu().numpy()
+    res["path"] = path.cpu().numpy()
+    return res
+
+
+def _load(root: str, kind: str, spk: str, base: str) -> np.ndarray:
+    fn = os.path.join(root, kind, f"{spk}-{kind}-{base}.npy")
+    if not os.path.exists(fn):
+        raise FileNotFoundError(f"objective evaluation needs the ground truth of every listed utterance: {fn} is missing")
+    return np.load(fn, allow_pickle=False)
+
+
+def _frames(values: np.ndarray, durations: np.ndarray, level: str, T: int, what: str) -> np.ndarray:
+    """A stored / predicted contour as T frame values: phoneme-level values repeated over their durations."""
+    v = np.asarray(values, np.float64).reshape(-1)
+    if level == "phoneme_level":
+        if v.shape[0] != durations.shape[0]:
+            raise ValueError(f"{what}: {v.shape[0]} phoneme values but {durations.shape[0]} durations")
+        v = np.repeat(v, durations)
+    if v.shape[0] < T:
+        raise ValueError(f"{what}: {v.shape[0]} frame values for {T} mel frames")
+    return v[:T]
+
+
+def _summary(rows: List[dict]) -> Dict:
+    out = {"n": len(rows), "n_empty": sum(1 for r in rows if r["pred_frames"] == 0), "mean": {}, "median": {}}
+    for m in METRICS:
+        v = np.asarray([r[m] for r in rows], np.float64)
+        v = v[~np.isnan(v)]
+        out["mean"][m] = float(v.mean()) if v.size else float("nan")
+        out["median"][m] = float(np.median(v)) if v.size else float("nan")
+    return out
+
+
+@torch.no_grad()
+def evaluate_objective(model, configs, source: str, device, controls=(1.0, 1.0, 1.0), batch_size: int = 32,
+                       out_dir: Optional[str] = None, n_ceps: int = 13) -> Dict:
+    """Free-running synthesis (no targets, predicted durations) of every utterance of ``source`` (a ``val.txt``-style
+    list) against its stored mel / pitch / energy / duration; one ``ops.dtw`` call per batch of pairs.
+    -> {"n", "n_empty", "mean": {metric: value}, "median": {...}}; with ``out_dir`` also ``objective_summary.json``
+    and the per-utterance ``objective.csv``."""
+    from torch.utils.data import DataLoader
+
+    from ..data.dataset import TextDataset, to_device
+
+    pp = configs[0]
+    root = pp["path"]["preprocessed_path"]
+    st = _stats(root)
+    levels = {"pitch": pp["preprocessing"]["pitch"]["feature"], "energy": pp["preprocessing"]["energy"]["feature"]}
+    ds = TextDataset(source, pp)
+    if len(ds) == 0:
+        raise ValueError(f"objective evaluation: {source} lists no utterances")
+    speaker_of = dict(zip(ds.basename, ds.speaker))
+    dev = torch.device(device)
+    model.eval()
+    rows: List[dict] = []
+    for batch in DataLoader(ds, batch_size=batch_size, collate_fn=ds.collate_fn):
+        names = batch[0]
+        truth = []
+        for base in names:  # fail on a missing file before the model runs
+            spk = speaker_of[base]
+            dur = _load(root, "duration", spk, base).astype(np.int64).reshape(-1)
+            mel = _load(root, "mel", spk, base).astype(np.float32)
+            T = min(mel.shape[0], int(dur.sum()))
+            if T < 1:
+                raise ValueError(f"objective evaluation: {base} has no frames in its stored mel / durations")
+            con = {k: _frames(_load(root, k, spk, base) * st[k][3] + st[k][2], dur, levels[k], T, f"{k} of {base}")
+                   for k in ("pitch", "energy")}
+            truth.append((mel[:T], con["pitch"], con["energy"], dur))
+        b = to_device(batch, dev)
+        out = model(*b[2:], p_control=controls[0], e_control=controls[1], d_control=controls[2])
+        post, p, e, d = out[1].float(), out[2].float().cpu().numpy(), out[3].float().cpu().numpy(), out[5].cpu().numpy()
+        src_lens, mel_lens = out[8].cpu().numpy(), out[9].cpu().numpy()
+        keep = [i for i in range(len(names)) if int(mel_lens[i]) > 0]
+        pred_con = {"pitch": [], "energy": []}
+        pred_dur = [d[i, :int(src_lens[i])].astype(np.int64) for i in range(len(names))]
+        for i, base in enumerate(names):
+            if pred_dur[i].shape != truth[i][3].shape:
+                raise ValueError(f"objective evaluation: {base} has {pred_dur[i].shape[0]} phonemes in {source} but "
+                                 f"{truth[i][3].shape[0]} stored durations")
+        for i in keep:
+            n, T = int(src_lens[i]), int(mel_lens[i])
+            for k, v in (("pitch", p), ("energy", e)):
+                vals = v[i, :n] if levels[k] == "phoneme_level" else v[i, :T]
+                pred_con[k].append(_frames(vals * st[k][3] + st[k][2], pred_dur[i], levels[k], T, f"predicted {k}"))
+        res = {}
+        if keep:
+            f64 = lambda xs: torch.from_numpy(np.concatenate(xs)).to(dev)  # noqa: E731
+            res = utterance_metrics(
+                torch.cat([post[i, :int(mel_lens[i])] for i in keep]).contiguous(), [int(mel_lens[i]) for i in keep],
+                torch.from_numpy(np.concatenate([truth[i][0] for i in keep])).to(dev), [truth[i][0].shape[0] for i in keep],
+                f64(pred_con["pitch"]), f64([truth[i][1] for i in keep]), f64(pred_con["energy"]),
+                f64([truth[i][2] for i in keep]), [pred_dur[i] for i in keep], [truth[i][3] for i in keep], n_ceps)
+        at = {i: k for k, i in enumerate(keep)}
+        for i, base in enumerate(names):
+            row = {"basename": base, "pred_frames": int(mel_lens[i]), "true_frames": int(truth[i][0].shape[0])}
+            for m in METRICS:
+                row[m] = float(res[m][at[i]]) if i in at else float("nan")
+            if i not in at:  # no alignment, but the duration figures stand
+                row["dur_mae_frames"] = float(np.abs(pred_dur[i] - truth[i][3]).mean())
+                row["len_ratio"] = 0.0
+            row["path_len"] = int(res["path_len"][at[i]]) if i in at else 0
+            rows.append(row)
+    summary = _summary(rows)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "objective_summary.json"), "w") as f:
+            json.dump(summary, f, indent=2)
+        with open(os.path.join(out_dir, "objective.csv"), "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=list(rows[0].keys()))
+            w.writeheader()
+            w.writerows(rows)
+    return summary

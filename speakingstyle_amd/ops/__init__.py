@@ -409,3 +409,12 @@ def griffin_lim(x, n_fft, hop, window, n_iters, momentum=0.99, init_phase=None, 
     fn = _hip().griffin_lim if use_hip(x) else ref.griffin_lim
     return fn(x, n_fft, hop, window, n_iters, momentum, init_phase, seed, lengths, int16_scale, mel_pinv, width,
               return_mag)
+
+
+def dtw(x, y, x_lens, y_lens, plane_budget=None):
+    """Dynamic time warping of P packed pairs (x [Rx, D] / y [Ry, D] rows, host row counts ``x_lens`` / ``y_lens``)
+    -> (cost [P], path [P, Lmax, 2] int32, path_len [P] int32); see ``ops.reference.dtw``.  On the GPU one
+    workgroup per pair (``csrc/k_dtw.hip``); ``plane_budget`` bounds the direction-plane bytes of one launch."""
+    if use_hip(x):
+        return _hip().dtw(x, y, x_lens, y_lens, plane_budget)
+    return ref.dtw(x, y, x_lens, y_lens)

@@ -2911,6 +2911,100 @@ def griffin_lim(x, n_fft, hop, window, n_iters, momentum=0.99, init_phase=None, 
     return (out, mag) if return_mag else out
 
 
+# ------------------------------------------------------------------------ dynamic time warping (csrc/k_dtw.hip)
+_SIGS.update({"ssamd_dtw_fwd": [P, P, P, P, P, I, I, I, P, P, P],
+              "ssamd_dtw_path": [P, P, P, P, I, I, P, P, P],
+              "ssamd_dtw_plane_bytes": [I, I],
+              "ssamd_dtw_max_ty": [I]})
+_RESTYPES.update({"ssamd_dtw_plane_bytes": L_, "ssamd_dtw_max_ty": L_})
+
+# Direction-plane budget of one dtw_fwd launch, in bytes of the stream's workspace: 256 MiB holds ~330 pairs of
+# 800 x 850 frames (a pair's plane is one byte per cell, rounded up to 64 x 64 tiles); a larger batch runs in
+# several launches over the same workspace.  A chunk always holds at least one pair, whatever its size.
+DTW_PLANE_BUDGET = 256 << 20
+
+
+def dtw_plane_bytes(tx: int, ty: int) -> int:
+    """csrc/dtw_index.h dtw_plane_bytes: strips of 64 rows x blocks of 64 wavefront steps (Ty + 63 per strip)."""
+    return ((tx + 63) // 64) * ((ty + 63 + 63) // 64) * 4096
+
+
+class DTWPlan:
+    """Device tables of a packed DTW batch, built from the host lengths and uploaded in one copy: ``cu_x`` / ``cu_y``
+    int32 [P + 1] row offsets, ``offs`` int64 [P] (viewed as int32 pairs) plane byte offsets, each chunk's counted
+    from 0, and ``chunks`` = (first pair, end pair, plane bytes) of consecutive pairs whose planes fit the budget."""
+
+    def __init__(self, xl, yl, device, plane_budget=None):
+        import numpy as np
+
+        budget = DTW_PLANE_BUDGET if plane_budget is None else int(plane_budget)
+        n = self.P = len(xl)
+        self.xl, self.yl = xl, yl
+        self.Lmax = (max(xl) + max(yl) - 1) if n else 0
+        off, p0, used = np.zeros(n, dtype=np.int64), 0, 0
+        self.chunks = []
+        for p in range(n):
+            size = dtw_plane_bytes(xl[p], yl[p])
+            if p > p0 and used + size > budget:
+                self.chunks.append((p0, p, used))
+                p0, used = p, 0
+            off[p] = used
+            used += size
+        if n:
+            self.chunks.append((p0, n, used))
+        cu = np.zeros(2 * (n + 1), dtype=np.int32)
+        cu[1:n + 1] = np.cumsum(xl)
+        cu[n + 2:] = np.cumsum(yl)
+        host = torch.from_numpy(np.concatenate([off.view(np.int32), cu]))
+        self.buf = (host.pin_memory() if device.type == "cuda" else host).to(device, non_blocking=True)
+        self.offs, self.cu_x, self.cu_y = self.buf[:2 * n], self.buf[2 * n:3 * n + 1], self.buf[3 * n + 1:]
+        self.ws_floats = (max([c[2] for c in self.chunks] + [0]) + 3) // 4
+
+
+def dtw_fwd_raw(x, y, plan, chunk, ws, cost):
+    """The forward launch of one chunk of ``plan``: direction planes into ``ws``, totals into ``cost`` [P]."""
+    a, b, _ = chunk
+    rc = lib().ssamd_dtw_fwd(_ptr(x), _ptr(y), _ptr(plan.cu_x[a:]), _ptr(plan.cu_y[a:]), _ptr(plan.offs[2 * a:]), b - a,
+                             x.shape[1], max(plan.yl[a:b]), _ptr(ws), _ptr(cost[a:]), _stream())
+    _check(rc, "ssamd_dtw_fwd")
+
+
+def dtw_path_raw(plan, chunk, ws, path, plen):
+    """The path launch of one chunk of ``plan``: walks the planes in ``ws`` into ``path`` [P, Lmax, 2] / ``plen`` [P]."""
+    a, b, _ = chunk
+    rc = lib().ssamd_dtw_path(_ptr(ws), _ptr(plan.offs[2 * a:]), _ptr(plan.cu_x[a:]), _ptr(plan.cu_y[a:]), b - a,
+                              plan.Lmax, _ptr(path[a:]), _ptr(plen[a:]), _stream())
+    _check(rc, "ssamd_dtw_path")
+
+
+def dtw(x, y, x_lens, y_lens, plane_budget=None):
+    """``ops.reference.dtw`` on the GPU (fp32, 1 <= D <= 80): one ``dtw_fwd`` launch (a workgroup per pair; direction
+    planes in the stream's workspace) and one ``dtw_path`` launch per chunk of pairs whose planes fit ``plane_budget``
+    bytes (default ``DTW_PLANE_BUDGET``).  ``x_lens`` / ``y_lens`` are host sequences: nothing here waits for the
+    device.  Every pair comes out bitwise as if alone.  -> cost [P] fp32, path [P, Lmax, 2] int32, path_len [P] int32."""
+    xl, yl = ref.dtw_lens(x, y, x_lens, y_lens)
+    _need(x, torch.float32, "dtw.x")
+    _need(y, torch.float32, "dtw.y")
+    npairs, D, dev = len(xl), x.shape[1], x.device
+    if not 1 <= D <= 80:
+        raise ValueError(f"dtw: feature size {D} not covered by the kernel (1 <= D <= 80)")
+    if npairs and max(yl) > int(lib().ssamd_dtw_max_ty(D)):
+        raise ValueError(f"dtw: a y of {max(yl)} rows exceeds the kernel's {int(lib().ssamd_dtw_max_ty(D))} at D = {D}")
+    if x.shape[0] >= 2 ** 31 or y.shape[0] >= 2 ** 31:
+        raise ValueError("dtw: packed row offsets are 32-bit")
+    plan = DTWPlan(xl, yl, dev, plane_budget)
+    cost = torch.empty(npairs, device=dev, dtype=torch.float32)
+    path = torch.empty(npairs, plan.Lmax, 2, device=dev, dtype=torch.int32)
+    plen = torch.empty(npairs, device=dev, dtype=torch.int32)
+    if npairs == 0:
+        return cost, path, plen
+    ws = _workspace(dev, plan.ws_floats)
+    for chunk in plan.chunks:  # the launches of a stream run in order: the next chunk reuses the planes
+        dtw_fwd_raw(x, y, plan, chunk, ws, cost)
+        dtw_path_raw(plan, chunk, ws, path, plen)
+    return cost, path, plen
+
+
 # ------------------------------------------------------------------------ N = 1 heads
 class _HeadFn(torch.autograd.Function):
     """Variance-predictor head Linear(C -> 1) + pad mask (one wave per row)."""

@@ -277,3 +277,85 @@ def griffin_lim(x, n_fft, hop, window, n_iters, momentum=0.99, init_phase=None, 
         wavs.append(y)
     out = _wav_batch(wavs, width, int16_scale, rows.dtype, rows.device)
     return (out, mag) if return_mag else out
+
+
+# ------------------------------------------------------------------ dynamic time warping (csrc/k_dtw.hip semantics)
+def dtw_lens(x, y, x_lens, y_lens):
+    """Host row counts of a packed DTW batch, validated: x [Rx, D] / y [Ry, D] with one (x_len, y_len) per pair.
+    A pair without rows on either side has no warping path: ``ValueError`` before anything runs."""
+    xl = [int(v) for v in (x_lens.tolist() if isinstance(x_lens, torch.Tensor) else x_lens)]
+    yl = [int(v) for v in (y_lens.tolist() if isinstance(y_lens, torch.Tensor) else y_lens)]
+    if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
+        raise ValueError(f"dtw: x / y must be packed rows [R, D] of one D, got {tuple(x.shape)} / {tuple(y.shape)}")
+    if len(xl) != len(yl):
+        raise ValueError(f"dtw: {len(xl)} x lengths but {len(yl)} y lengths")
+    for p, (a, b) in enumerate(zip(xl, yl)):
+        if a < 1 or b < 1:
+            raise ValueError(f"dtw: pair {p} has lengths ({a}, {b}); every pair needs at least one row on each side")
+    if sum(xl) != x.shape[0] or sum(yl) != y.shape[0]:
+        raise ValueError(f"dtw: lengths sum to ({sum(xl)}, {sum(yl)}) but x / y have ({x.shape[0]}, {y.shape[0]}) rows")
+    return xl, yl
+
+
+def _dtw_one(x, y):
+    """One pair: (A(Tx-1, Ty-1) as a 0-d tensor, directions [Tx, Ty] uint8) by a wavefront over the anti-diagonals
+    (one batch of elementwise ops per diagonal)."""
+    Tx, Ty, W = x.shape[0], y.shape[0], y.shape[0] + 1
+    c = torch.zeros(Tx, Ty, dtype=x.dtype, device=x.device)
+    for d in range(x.shape[1]):  # from the differences, d in index order
+        df = x[:, d].unsqueeze(1) - y[:, d].unsqueeze(0)
+        c = c + df * df
+    c = torch.sqrt(c).reshape(-1)
+    A = torch.full(((Tx + 1) * W,), float("inf"), dtype=x.dtype, device=x.device)  # cell (i, j) at (i+1) W + j + 1
+    A[0] = 0.0  # the diagonal predecessor of (0, 0)
+    dirs = torch.zeros(Tx * Ty, dtype=torch.uint8, device=x.device)
+    two = torch.full((), 2, dtype=torch.uint8, device=x.device)
+    for k in range(Tx + Ty - 1):
+        lo, hi = max(0, k - Ty + 1), min(k, Tx - 1)
+        n = hi - lo + 1
+        at = (lo + 1) * W + (k - lo) + 1  # cells of diagonal k: stride W - 1 in A, Ty - 1 in c / dirs
+        diag = torch.as_strided(A, (n,), (W - 1,), at - W - 1)
+        up = torch.as_strided(A, (n,), (W - 1,), at - W)
+        left = torch.as_strided(A, (n,), (W - 1,), at - 1)
+        # tie rule: diagonal, then (i-1, j), then (i, j-1); a later candidate wins only on strict <
+        m1 = up < diag
+        best = torch.where(m1, up, diag)
+        m2 = left < best
+        best = torch.where(m2, left, best)
+        ck = torch.as_strided(c, (n,), (Ty - 1,), lo * Ty + k - lo)
+        torch.as_strided(A, (n,), (W - 1,), at).copy_(ck + best)
+        torch.as_strided(dirs, (n,), (Ty - 1,), lo * Ty + k - lo).copy_(torch.where(m2, two, m1.to(torch.uint8)))
+    return A[-1], dirs.view(Tx, Ty)
+
+
+def dtw(x, y, x_lens, y_lens):
+    """Dynamic time warping of P packed pairs: x [Rx, D] / y [Ry, D] rows, ``x_lens`` / ``y_lens`` the P row counts
+    (host sequences).  Local cost c(i, j) = sqrt(sum_d (x[i, d] - y[j, d])^2) from the differences; A(i, j) =
+    c(i, j) + min(A(i-1, j-1), A(i-1, j), A(i, j-1)) with ties to the diagonal, then (i-1, j), then (i, j-1).
+    Computes in x's dtype (float64 = the oracle) on x's device.
+    -> cost [P] = A(Tx-1, Ty-1), path [P, Lmax, 2] int32 ((i, j) cells in increasing order, -1 past the length,
+    Lmax = max Tx + max Ty - 1), path_len [P] int32."""
+    import numpy as np
+
+    xl, yl = dtw_lens(x, y, x_lens, y_lens)
+    P = len(xl)
+    Lmax = (max(xl) + max(yl) - 1) if P else 0
+    path = np.full((P, Lmax, 2), -1, dtype=np.int32)
+    plen = np.zeros(P, dtype=np.int32)
+    costs, ox, oy = [], 0, 0
+    for p, (tx, ty) in enumerate(zip(xl, yl)):
+        total, dirs = _dtw_one(x[ox:ox + tx], y[oy:oy + ty].to(x.dtype))
+        ox, oy = ox + tx, oy + ty
+        costs.append(total)
+        dr = dirs.cpu().numpy()
+        i, j, cells = tx - 1, ty - 1, []
+        while True:
+            cells.append((i, j))
+            if i == 0 and j == 0:
+                break
+            d = dr[i, j]
+            i, j = (i - 1 if d != 2 else i), (j - 1 if d != 1 else j)
+        plen[p] = len(cells)
+        path[p, :len(cells)] = np.asarray(cells[::-1], dtype=np.int32)
+    cost = torch.stack(costs) if P else torch.zeros(0, dtype=x.dtype, device=x.device)
+    return cost, torch.from_numpy(path).to(x.device), torch.from_numpy(plen).to(x.device)

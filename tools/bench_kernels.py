@@ -3,7 +3,7 @@
 
 Reports achieved TFLOP/s (GEMM-shaped) or GB/s (memory-bound) per kernel, and
 the hipBLASLt number for the plain-GEMM equivalent (torch.matmul) as a yardstick.
-Usage (GPU box): python tools/bench_kernels.py [--rows 160000] [--iters 20]
+Usage (GPU box): python tools/bench_kernels.py [--rows 160000] [--iters 20] | --griffin-lim | --dtw
 """
 import argparse
 import json
@@ -102,6 +102,88 @@ def bench_griffin_lim(out_path, rounds=7, n_iters=60):
             f.write(text)
 
 
+def dtw_workloads():
+    """(name, x, y, x_lens, y_lens) on the CPU: 64 pairs with the LJSpeech ``val.txt`` frame-count distribution
+    (phoneme counts x 8.1 frames, as data/synthetic.py draws them) and a +-10 % length mismatch, and one 800 x 850
+    pair; D = 13, y a time-warped copy of x plus 0.3 x noise."""
+    import numpy as np
+
+    from speakingstyle_amd.data import synthetic
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    counts = synthetic.ljspeech_phone_counts(os.path.join(root, "preprocessed_data", "LJSpeech", "val.txt"))
+    rng = np.random.default_rng(0)
+    tx = np.clip(np.round(rng.choice(counts, size=64) * 8.1), 16, 1000).astype(np.int64)
+    ty = np.maximum(1, np.round(tx * rng.uniform(0.9, 1.1, size=64))).astype(np.int64)
+    out = []
+    for name, xl, yl in (("64 pairs, LJSpeech val lengths +-10 %", tx.tolist(), ty.tolist()), ("1 pair, 800 x 850", [800], [850])):
+        g = torch.Generator().manual_seed(len(xl))
+        xs, ys = [], []
+        for a, b in zip(xl, yl):
+            x = torch.randn(a, 13, generator=g)
+            src = torch.round(torch.arange(b, dtype=torch.float64) * ((a - 1) / max(b - 1, 1))).long()
+            xs.append(x)
+            ys.append(x[src] + 0.3 * torch.randn(b, 13, generator=g))
+        out.append((name, torch.cat(xs), torch.cat(ys), xl, yl))
+    return out
+
+
+def bench_dtw(out_path, rounds=3):
+    """``ops.dtw`` (csrc/k_dtw.hip: one fwd + one path launch) against the torch wavefront of ``ops/reference.py``
+    on the same GPU tensors.  The two arms alternate in one process; every call is timed wall-clock between two device
+    synchronisations (the torch arm walks its paths on the host).  The fwd and path kernels are also timed on
+    their own with device events."""
+    import time
+
+    from speakingstyle_amd import ops
+    from speakingstyle_amd.ops import reference as ref
+
+    dev = torch.device("cuda")
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    lines = [f"Batched DTW, D = 13, fp32, {torch.cuda.get_device_name(0)}",
+             f"{rounds} alternating rounds per arm after 1 warm-up round; wall time per call between device syncs (ms);",
+             "kernel rows: device-event time of one launch (3 warm-up launches before each), 20 samples", "",
+             f"{'workload':40s} {'arm':>24s} {'median':>10s} {'min':>10s} {'max':>10s}"]
+    for name, x, y, xl, yl in dtw_workloads():
+        x, y = x.to(dev), y.to(dev)
+        t = {"hip ops.dtw": [], "torch wavefront": []}
+        for r in range(rounds + 1):
+            for arm, fn in (("hip ops.dtw", lambda: ops.dtw(x, y, xl, yl)), ("torch wavefront", lambda: ref.dtw(x, y, xl, yl))):
+                ms = wall(fn)
+                if r >= 1:
+                    t[arm].append(ms)
+        for arm, v in t.items():
+            v.sort()
+            lines.append(f"{name:40s} {arm:>24s} {v[len(v) // 2]:10.3f} {v[0]:10.3f} {v[-1]:10.3f}")
+        a, b = t["hip ops.dtw"], t["torch wavefront"]
+        lines.append(f"{'':40s} {'torch / hip (medians)':>24s} {b[len(b) // 2] / a[len(a) // 2]:10.1f}")
+        lines.append(f"{'':40s} {'slowest hip < fastest torch':>24s} {str(a[-1] < b[0]):>10s}")
+        plan = hip.DTWPlan(xl, yl, dev)
+        ws = hip._workspace(dev, plan.ws_floats)
+        cost = torch.empty(plan.P, device=dev)
+        path = torch.empty(plan.P, plan.Lmax, 2, device=dev, dtype=torch.int32)
+        plen = torch.empty(plan.P, device=dev, dtype=torch.int32)
+        assert len(plan.chunks) == 1
+        for arm, fn in (("dtw_fwd kernel", lambda: hip.dtw_fwd_raw(x, y, plan, plan.chunks[0], ws, cost)),
+                        ("dtw_path kernel", lambda: hip.dtw_path_raw(plan, plan.chunks[0], ws, path, plen))):
+            v = sorted(timeit(fn, 1) for _ in range(20))
+            lines.append(f"{name:40s} {arm:>24s} {v[len(v) // 2]:10.3f} {v[0]:10.3f} {v[-1]:10.3f}")
+        lines.append(f"{'':40s} cells: {sum(a * b for a, b in zip(xl, yl))}, plane bytes: {plan.chunks[0][2]}")
+    text = "\n".join(lines) + "\n"
+    print(text, end="", flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=160000)
@@ -109,9 +191,14 @@ def main():
     ap.add_argument("--only-attn", action="store_true")
     ap.add_argument("--griffin-lim", action="store_true",
                     help="only the Griffin-Lim arm: HIP kernels vs the torch loop, table written to --out")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                                  "profiles", "griffin_lim.txt"))
+    ap.add_argument("--dtw", action="store_true",
+                    help="only the DTW arm: HIP kernels vs the torch wavefront, table written to --out")
+    ap.add_argument("--out", default=None, help="default: profiles/griffin_lim.txt, profiles/dtw.txt")
     args = ap.parse_args()
+    prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    if args.dtw:
+        return bench_dtw(args.out or os.path.join(prof, "dtw.txt"))
+    args.out = args.out or os.path.join(prof, "griffin_lim.txt")
     if args.griffin_lim:
         return bench_griffin_lim(args.out)
     dev = "cuda"
