@@ -94,6 +94,8 @@ def tiny_overrides(mc):
     if mc.get("gst"):
         mc["gst"].update(conv_filters=[4, 4, 8, 8, 16, 16], gru_hidden=16, token_size=16, n_style_token=4,
                          attn_head=2)
+    if mc.get("aligner"):
+        mc["aligner"]["hidden"] = 32
 
 
 # ---------------------------------------------------------------------- outputs
@@ -133,7 +135,7 @@ def dump_outputs(out_dir, result):
 def train_phase(args, rank, world, device):
     import torch
 
-    from .config import load_named
+    from .config import learned_durations, load_named
     from .data.synthetic import SyntheticBatches
     from .models.fastspeech2 import FastSpeech2
     from .parallel import ddp
@@ -165,7 +167,8 @@ def train_phase(args, rank, world, device):
     budget = getattr(args, "frames_per_gpu", None)
     gen = SyntheticBatches(batch, device=device, max_seq_len=mc["max_seq_len"], seed=1000 + rank, n_speakers=n_spk,
                            frames_per_batch=budget,
-                           frame_level=pp["preprocessing"]["pitch"]["feature"] == "frame_level")
+                           frame_level=pp["preprocessing"]["pitch"]["feature"] == "frame_level",
+                           learned_durations=learned_durations(pp))
     pool = []
     for _ in range(args.pool):
         b = gen.make_batch()

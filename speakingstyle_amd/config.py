@@ -54,6 +54,9 @@ _MODEL_DEFAULTS: Config = {
     # condition on preprocessing.speaker_embedder vectors through a learned projection (not in the
     # reference model: its checkpoints lack the projection, so this is opt-in)
     "speaker_embed_proj": False,
+    # alignment learner (models/aligner.py): {hidden, temperature, prior_scaling}; None => durations come with the
+    # data (no extra parameters: reference checkpoints load as before)
+    "aligner": None,
     "max_seq_len": 1000,
     "vocoder": {"model": "HiFi-GAN", "speaker": "LJSpeech"},
 }
@@ -134,6 +137,9 @@ _PREPROCESS_DEFAULTS: Config = {
         "mel": {"n_mel_channels": 80, "mel_fmin": 0, "mel_fmax": 8000},
         "pitch": {"feature": "phoneme_level", "normalization": True, "extractor": "dio"},
         "energy": {"feature": "phoneme_level", "normalization": True},
+        # textgrid: phoneme durations from Montreal-Forced-Aligner TextGrids; learned: no TextGrids -- phones from
+        # the transcript, frame-level contours, durations from the model's alignment learner
+        "duration": {"source": "textgrid"},
         "speaker_embedder": "none",
     },
 }
@@ -167,6 +173,7 @@ def normalize_preprocess_config(cfg: Config | None) -> Config:
     _check_enum(pp["pitch"]["feature"], ["phoneme_level", "frame_level"], "preprocessing.pitch.feature")
     _check_enum(pp["pitch"].get("extractor", "dio"), ["dio", "yin"], "preprocessing.pitch.extractor")
     _check_enum(pp["energy"]["feature"], ["phoneme_level", "frame_level"], "preprocessing.energy.feature")
+    _check_enum(pp["duration"]["source"], ["textgrid", "learned"], "preprocessing.duration.source")
     return out
 
 
@@ -182,6 +189,12 @@ def normalize_model_config(cfg: Config | None) -> Config:
         out["gst"] = _merge(_GST_DEFAULTS, gst)
         if not out["gst"].get("use_gst", False):
             out["gst"] = None
+    if out.get("aligner"):
+        missing = [k for k in ("hidden", "temperature", "prior_scaling") if k not in out["aligner"]]
+        if missing:
+            raise ConfigError(f"aligner block lacks {missing}")
+        if int(out["aligner"]["hidden"]) % 8:
+            raise ConfigError("aligner.hidden must be a multiple of 8")
     tr = out["transformer"]
     for side in ("encoder", "decoder"):
         if tr[f"{side}_hidden"] % tr[f"{side}_head"]:
@@ -197,6 +210,7 @@ def normalize_train_config(cfg: Config | None) -> Config:
     # (model/optimizer.py:16); without a loss block fall back to warm_up_step.
     loss = out.get("loss") or {}
     loss.setdefault("lambda_f", 0.0)
+    loss.setdefault("lambda_align", 1.0)  # weight of the forward-sum alignment loss (learned durations only)
     loss.setdefault("anneal_steps", out["optimizer"]["warm_up_step"])
     out["loss"] = loss
     if out["optimizer"]["grad_acc_step"] < 1:
@@ -211,6 +225,12 @@ def normalize_train_config(cfg: Config | None) -> Config:
     if "nan_guard" in mi:  # removed knob: the device-side non-finite skip is unconditional
         mi.pop("nan_guard")
     return out
+
+
+def learned_durations(preprocess_config: Config) -> bool:
+    """``preprocessing.duration.source: learned``: no TextGrids and no ``duration/`` arrays; the model's alignment
+    learner supplies the durations (``models/aligner.py``)."""
+    return ((preprocess_config.get("preprocessing") or {}).get("duration") or {}).get("source", "textgrid") == "learned"
 
 
 def style_mode(model_config: Config) -> str:

@@ -2,7 +2,9 @@
 
 ``{preprocessed_path}/{train,val}.txt`` lines ``basename|speaker|{PH ...}|raw``,
 per-utterance ``mel/{spk}-mel-{base}.npy`` ([T,80] f32), ``pitch/``, ``energy/``,
-``duration/`` arrays, ``speakers.json``.  Behaviour follows the reference's
+``duration/`` arrays, ``speakers.json`` (with ``preprocessing.duration.source: learned`` there is no ``duration/``,
+``pitch/`` and ``energy/`` hold frame-level contours and the batch carries ``None`` for the durations).
+Behaviour follows the reference's
 ``dataset.py:12-218``: the train collate sorts a group by text length
 (descending), splits it into ``batch_size`` chunks and drops the tail when
 ``drop_last``.  Differences: padding is done by one vectorised C++ routine when
@@ -21,6 +23,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset as _TorchDataset
 
+from ..config import learned_durations
 from ..text import text_to_sequence
 from ..utils.tools import pad_1d, pad_2d
 
@@ -47,6 +50,7 @@ class Dataset(_TorchDataset):
         self.preprocessed_path = preprocess_config["path"]["preprocessed_path"]
         self.cleaners = preprocess_config["preprocessing"]["text"]["text_cleaners"]
         self.batch_size = train_config["optimizer"]["batch_size"]
+        self.learned = learned_durations(preprocess_config)
         self.basename, self.speaker, self.text, self.raw_text = read_meta(os.path.join(self.preprocessed_path, filename))
         with open(os.path.join(self.preprocessed_path, "speakers.json")) as f:
             self.speaker_map = json.load(f)
@@ -71,7 +75,7 @@ class Dataset(_TorchDataset):
             "mel": self._npy("mel", spk, base).astype(np.float32),
             "pitch": self._npy("pitch", spk, base).astype(np.float32),
             "energy": self._npy("energy", spk, base).astype(np.float32),
-            "duration": self._npy("duration", spk, base).astype(np.int64),
+            "duration": None if self.learned else self._npy("duration", spk, base).astype(np.int64),
         }
 
     def reprocess(self, data, idxs):
@@ -92,7 +96,7 @@ class Dataset(_TorchDataset):
             int(mel_lens.max()),
             pad_1d([d["pitch"] for d in items]),
             pad_1d([d["energy"] for d in items]),
-            pad_1d([d["duration"] for d in items]),
+            None if self.learned else pad_1d([d["duration"] for d in items]),
         )
 
     def collate_fn(self, data):
@@ -305,9 +309,13 @@ def to_device(batch, device):
         # host copy of the lengths: sizes the packed decoder (models/fastspeech2.py) without a sync
         if not (isinstance(mel_lens, torch.Tensor) and mel_lens.is_cuda):
             ml.host_lengths = np.asarray(mel_lens.numpy() if isinstance(mel_lens, torch.Tensor) else mel_lens)
-        return (ids, raw, t(spk, torch.long), t(texts, torch.long), t(src_lens, torch.long), max_src,
+        sl = t(src_lens, torch.long)
+        if d is None and not (isinstance(src_lens, torch.Tensor) and src_lens.is_cuda):
+            # learned durations: the alignment ops check T >= N on the host
+            sl.host_lengths = np.asarray(src_lens.numpy() if isinstance(src_lens, torch.Tensor) else src_lens)
+        return (ids, raw, t(spk, torch.long), t(texts, torch.long), sl, max_src,
                 t(mels, torch.float32), ml, max_mel, t(p, torch.float32), t(e, torch.float32),
-                t(d, torch.long))
+                None if d is None else t(d, torch.long))
     if len(batch) == 9:
         ids, raw, spk, texts, src_lens, max_src, mels, mel_lens, max_mel = batch
         return (ids, raw, t(spk, torch.long), t(texts, torch.long), t(src_lens, torch.long), max_src,

@@ -16,6 +16,11 @@ unpinned (the library is not installable here).  ``preprocessing.pitch.extractor
 yin`` selects the vectorised YIN tracker below instead.
 Utterances are processed by a multiprocessing pool (the reference uses
 joblib+dask, ``preprocessor/bc_2013.py:62-73``).
+
+``preprocessing.duration.source: learned`` needs no aligner run and no TextGrids: the phones come from the
+transcript through the text frontend (what ``synthesize.py`` feeds the model), the whole utterance's mel is
+stored with frame-level energy and interpolated-F0 contours under ``energy/`` and ``pitch/``, and there is no
+``duration/``: the model's alignment learner finds the durations in training (``models/aligner.py``).
 """
 from __future__ import annotations
 
@@ -213,6 +218,10 @@ class Preprocessor:
         self.pitch_norm = pp["pitch"]["normalization"]
         self.energy_norm = pp["energy"]["normalization"]
         self.f0_method = pp["pitch"].get("extractor", "dio")
+        self.learned = (pp.get("duration") or {}).get("source", "textgrid") == "learned"
+        self.language = pp["text"].get("language", "en")
+        self.cleaners = pp["text"]["text_cleaners"]
+        self._lexicon = None
         self.stft = TacotronSTFT(pp["stft"]["filter_length"], self.hop_length, pp["stft"]["win_length"],
                                  pp["mel"]["n_mel_channels"], self.sampling_rate, pp["mel"]["mel_fmin"],
                                  pp["mel"]["mel_fmax"])
@@ -244,8 +253,49 @@ class Preprocessor:
             np.save(os.path.join(self.out_dir, kind, f"{speaker}-{kind}-{basename}.npy"), arr)
         return "|".join([basename, speaker, text, raw_text]), remove_outlier(pitch), remove_outlier(energy), mel.shape[1]
 
+    def transcript_phones(self, raw_text: str) -> List[str]:
+        """Phones of a transcript through the text frontend, as synthesis produces them (lexicon + letter-to-sound
+        for English, the pinyin lexicon for Mandarin)."""
+        from ..text import g2p
+
+        if self._lexicon is None:
+            self._lexicon = g2p.load_lexicon(self.config["path"]["lexicon_path"], self.language)
+        if self.language == "zh":
+            return g2p.mandarin_phones(raw_text.split(), self._lexicon)
+        return g2p.english_to_phones(raw_text, self._lexicon)
+
+    def process_utterance_unaligned(self, speaker: str, basename: str):
+        """``duration.source: learned``: phones from the transcript, the whole utterance's mel, frame-level energy
+        and interpolated F0.  -> the ``process_utterance`` tuple, None (no usable pitch / no phones), or
+        ``"short"`` for an utterance with fewer frames than phones (no monotone alignment exists)."""
+        from ..text import text_to_sequence
+
+        wav_path = os.path.join(self.in_dir, speaker, f"{basename}.wav")
+        lab_path = os.path.join(self.in_dir, speaker, f"{basename}.lab")
+        with open(lab_path, encoding="utf-8") as f:
+            raw_text = f.readline().strip("\n")
+        phone = self.transcript_phones(raw_text)
+        text = "{" + " ".join(phone) + "}"
+        n_phone = len(text_to_sequence(text, self.cleaners))
+        if n_phone == 0:
+            return None
+        wav, _ = read_wav(wav_path, self.sampling_rate)
+        wav = wav.astype(np.float32)
+        pitch = extract_f0(wav, self.sampling_rate, self.hop_length, self.f0_method)
+        mel, energy = get_mel_from_wav(np.clip(wav, -1, 1), self.stft)
+        T = min(mel.shape[1], pitch.shape[0])
+        pitch, mel, energy = pitch[:T], mel[:, :T], energy[:T]
+        if T < n_phone:
+            return "short"
+        if np.sum(pitch != 0) <= 1:
+            return None
+        pitch = interpolate_unvoiced(pitch)
+        for kind, arr in (("pitch", pitch), ("energy", energy), ("mel", mel.T)):
+            np.save(os.path.join(self.out_dir, kind, f"{speaker}-{kind}-{basename}.npy"), arr)
+        return "|".join([basename, speaker, text, raw_text]), remove_outlier(pitch), remove_outlier(energy), mel.shape[1]
+
     def build_from_path(self, workers: int = 4):
-        for kind in ("mel", "pitch", "energy", "duration"):
+        for kind in ("mel", "pitch", "energy") + (() if self.learned else ("duration",)):
             os.makedirs(os.path.join(self.out_dir, kind), exist_ok=True)
         speakers = {}
         jobs: List[Tuple[str, str]] = []
@@ -257,17 +307,24 @@ class Preprocessor:
             for fn in sorted(os.listdir(spk_dir)):
                 if fn.endswith(".wav"):
                     base = fn[:-4]
-                    if os.path.exists(os.path.join(self.out_dir, "TextGrid", spk, f"{base}.TextGrid")):
+                    if self.learned:
+                        if os.path.exists(os.path.join(spk_dir, f"{base}.lab")):
+                            jobs.append((spk, base))
+                    elif os.path.exists(os.path.join(self.out_dir, "TextGrid", spk, f"{base}.TextGrid")):
                         jobs.append((spk, base))
+        one = self.process_utterance_unaligned if self.learned else self.process_utterance
         if workers > 1:
             with Pool(workers) as pool:
-                results = pool.starmap(self.process_utterance, jobs)
+                results = pool.starmap(one, jobs)
         else:
-            results = [self.process_utterance(s, b) for s, b in jobs]
+            results = [one(s, b) for s, b in jobs]
         out, pm, em = [], RunningMoments(), RunningMoments()
         n_frames = 0
+        n_short = sum(1 for r in results if isinstance(r, str))
+        if n_short:
+            print(f"Dropped {n_short} utterances with fewer mel frames than phones")
         for r in results:
-            if r is None:
+            if r is None or isinstance(r, str):
                 continue
             info, p, e, n = r
             out.append(info)

@@ -18,6 +18,10 @@ into batches whose PADDED frame count ``n * max(len)`` stays within the budget
 (the PostNet runs on the padded layout, so that is the memory-relevant size);
 the utterance count per batch then varies with the lengths.  ``n_speakers > 1``
 draws speaker ids uniformly (multi-speaker configs, e.g. LibriTTS's 904).
+
+``learned_durations`` (``preprocessing.duration.source: learned``): the batch carries no durations (``None``)
+and pitch / energy are frame-level contours [B, M], as the unaligned preprocessor stores them; the model's
+alignment learner supplies the durations.
 """
 from __future__ import annotations
 
@@ -50,8 +54,9 @@ class SyntheticBatches:
     def __init__(self, batch_size: int, device="cpu", n_mel: int = 80, n_speakers: int = 1, max_seq_len: int = 1000,
                  pitch_range=(-2.9, 11.4), energy_range=(-1.4, 8.2), frame_level: bool = False, group_size: int = 4,
                  seed: int = 1234, frames_per_phone: float = 8.1, vocab: int = 360, phone_counts=None,
-                 frames_per_batch: Optional[int] = None):
+                 frames_per_batch: Optional[int] = None, learned_durations: bool = False):
         self.B = batch_size
+        self.learned = bool(learned_durations)
         self.frame_budget = int(frames_per_batch) if frames_per_batch else None
         if self.frame_budget is not None and self.frame_budget < max_seq_len:
             raise ValueError(f"frames_per_batch={self.frame_budget} cannot hold one utterance of up to "
@@ -149,8 +154,9 @@ class SyntheticBatches:
         texts = torch.randint(1, self.vocab + 1, (B, T), generator=g)
         src_valid = torch.arange(T).unsqueeze(0) < torch.from_numpy(Ts).unsqueeze(1)
         texts = texts * src_valid
-        L_p = M if self.frame_level else T
-        pv = torch.arange(L_p).unsqueeze(0) < torch.from_numpy(mel_lens if self.frame_level else Ts).unsqueeze(1)
+        contours = self.frame_level or self.learned
+        L_p = M if contours else T
+        pv = torch.arange(L_p).unsqueeze(0) < torch.from_numpy(mel_lens if contours else Ts).unsqueeze(1)
         pitch = (torch.randn(B, L_p, generator=g).clamp(*self.pitch_range)) * pv
         energy = (torch.randn(B, L_p, generator=g).clamp(*self.energy_range)) * pv
         mel_valid = torch.arange(M).unsqueeze(0) < torch.from_numpy(mel_lens).unsqueeze(1)
@@ -163,6 +169,11 @@ class SyntheticBatches:
         ids = [f"synth_{i}" for i in range(B)]
         ml = tt(torch.from_numpy(mel_lens))
         ml.host_lengths = mel_lens  # host copy: sizes the packed decoder without a device sync
+        if self.learned:
+            sl = tt(torch.from_numpy(Ts))
+            sl.host_lengths = Ts  # the alignment ops check T >= N on the host
+            return (ids, ["" for _ in range(B)], tt(speakers), tt(texts), sl, T, tt(mels), ml, M, tt(pitch),
+                    tt(energy), None)
         return (ids, ["" for _ in range(B)], tt(speakers), tt(texts), tt(torch.from_numpy(Ts)), T, tt(mels),
                 ml, M, tt(pitch), tt(energy), tt(torch.from_numpy(dur)))
 

@@ -369,6 +369,13 @@ class FastSpeech2(nn.Module):
         if table is not None:
             self.register_buffer("spker_table", table, persistent=False)
             self.spker_embed_proj = nn.Linear(table.shape[1], d)
+        # alignment learner (model.yaml ``aligner:`` block; absent by default): durations for teacher forcing come
+        # from its Viterbi path when the batch carries none (preprocessing.duration.source: learned)
+        self.aligner = None
+        if model_config.get("aligner"):
+            from .aligner import AlignmentEncoder
+
+            self.aligner = AlignmentEncoder(n_mel, d, model_config["aligner"])
         self.compute_dtype = torch.float32
 
     # ------------------------------------------------------------------ helpers
@@ -436,6 +443,11 @@ class FastSpeech2(nn.Module):
             mel_lens_host = getattr(mel_lens, "host_lengths", None)
         if mels is not None and max_mel_len is None:
             max_mel_len = mels.shape[1]
+        align = None
+        if d_targets is None and (p_targets is not None or e_targets is not None):
+            # teacher forcing without durations: they are learned (MAS over the aligner's lattice)
+            align = self.learn_alignment(texts, src_lens, mels, mel_lens, mel_lens_host, p_targets, e_targets)
+            d_targets, p_targets, e_targets = align["durations"], align["p_targets"], align["e_targets"]
         style = self.compute_style(mels, mel_lens, max_mel_len, texts.shape[0], dev, style_weights)
         x = self.encoder(texts, src_lens, style, cd)
         if self.speaker_emb is not None:
@@ -464,7 +476,38 @@ class FastSpeech2(nn.Module):
         post = self.postnet(mel.to(cd)).float() + mel
         src_masks = ops.lengths_to_mask(src_lens, texts.shape[1])
         mel_masks = ops.lengths_to_mask(dec_lens, mel.shape[1])
-        return (mel, post, p_pred, e_pred, log_d, d_rounded, src_masks, mel_masks, src_lens, mel_lens_out)
+        out = (mel, post, p_pred, e_pred, log_d, d_rounded, src_masks, mel_masks, src_lens, mel_lens_out)
+        # learned-duration mode only: the alignment terms travel as one extra element (FastSpeech2Loss reads it)
+        return out if align is None else out + (align,)
+
+    def learn_alignment(self, texts, src_lens, mels, mel_lens, mel_lens_host, p_targets, e_targets):
+        """Teacher forcing from a batch without durations: the aligner's lattice lp [B, T, N] (differentiable: the
+        forward-sum loss trains it), its MAS durations (no gradient; they sum to ``mel_lens``) and the frame-level
+        pitch / energy contours averaged over each token's frames where the feature is phoneme-level.
+        The keys read the phoneme embedding table without sending a gradient into it: the table is trained by the
+        synthesis losses alone.
+        -> {"lp", "t_lens", "n_lens", "durations", "p_targets", "e_targets"}"""
+        if self.aligner is None:
+            raise ValueError("the batch has mel / pitch / energy targets but no durations, and the model has no "
+                             "aligner: add an `aligner:` block to model.yaml (config/LJSpeech_unaligned) or provide "
+                             "durations")
+        if mels is None or mel_lens is None:
+            raise ValueError("learned durations need the target mel and its lengths")
+        cd = self.compute_dtype
+        emb = F.embedding(texts, self.encoder.src_word_emb.weight.detach()).to(cd)
+        lp = self.aligner(mels.to(cd), mel_lens, emb, src_lens)
+        t_lens = mel_lens
+        if getattr(mel_lens, "host_lengths", None) is None and mel_lens_host is not None:
+            t_lens = [int(v) for v in mel_lens_host]  # host lengths: the ops' checks need no device sync
+        with torch.no_grad():
+            dur = ops.align_mas(lp.detach(), t_lens, src_lens)
+            va = self.variance_adaptor
+            if p_targets is not None and va.pitch_feature_level == "phoneme_level":
+                p_targets = ops.segment_mean(p_targets, dur)
+            if e_targets is not None and va.energy_feature_level == "phoneme_level":
+                e_targets = ops.segment_mean(e_targets, dur)
+        return {"lp": lp, "t_lens": t_lens, "n_lens": src_lens, "durations": dur, "p_targets": p_targets,
+                "e_targets": e_targets}
 
     def packed_inference_ok(self, texts) -> bool:
         return (not self.training and ops.use_hip(texts) and self.variance_adaptor.packable()

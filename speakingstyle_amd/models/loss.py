@@ -10,6 +10,9 @@ same 7-tuple output.  Implementation differences:
   masked sums by the counts of the whole global batch (all-reduced), so summed
   gradients equal the single-process full-batch gradient (the reference computes
   the loss on the DataParallel-gathered full batch, ``train.py:86-88``).
+* learned durations (the model's output carries an eleventh element, ``FastSpeech2.learn_alignment``): the
+  duration / pitch / energy targets are the ones the model derived from its MAS alignment, and the forward-sum
+  alignment loss ``lambda_align * mean_b(nll_b / N_b)`` is added and reported as an eighth entry.
 """
 from __future__ import annotations
 
@@ -29,6 +32,7 @@ class FastSpeech2Loss(nn.Module):
         self.energy_feature_level = pp["energy"]["feature"]
         loss_cfg = train_config.get("loss") or {}
         self.lambda_f = float(loss_cfg.get("lambda_f", 0.0))
+        self.lambda_align = float(loss_cfg.get("lambda_align", 1.0))
 
     @staticmethod
     def local_counts(batch, predictions, n_mel):
@@ -41,7 +45,10 @@ class FastSpeech2Loss(nn.Module):
     def forward(self, inputs, predictions, named_param: Optional[torch.Tensor] = None,
                 global_counts: Optional[torch.Tensor] = None):
         mel_t, _, _, p_t, e_t, d_t = inputs[6:12]
-        mel_p, post_p, p_p, e_p, logd_p, _, src_masks, mel_masks, _, _ = predictions
+        align = predictions[10] if len(predictions) > 10 else None
+        if align is not None:  # learned durations: the targets the model derived from its own alignment
+            p_t, e_t, d_t = align["p_targets"], align["e_targets"], align["durations"]
+        mel_p, post_p, p_p, e_p, logd_p, _, src_masks, mel_masks, _, _ = predictions[:10]
         M = mel_masks.shape[1]
         mel_t = mel_t[:, :M]
         n_mel = mel_t.shape[-1]
@@ -63,7 +70,7 @@ class FastSpeech2Loss(nn.Module):
                 src_masks if phon_e else mel_masks, logd_p, d_t, src_masks, mel_count=c_mel, var_counts=gc)
             if named_param is not None and self.lambda_f > 0:
                 total = total + self.lambda_f * torch.sum(torch.square(named_param))
-            return total, mel_l, post_l, pitch_l, energy_l, dur_l, self.lambda_f
+            return self._with_alignment(align, (total, mel_l, post_l, pitch_l, energy_l, dur_l, self.lambda_f))
         else:
             src_valid = ~src_masks
             mel_valid = ~mel_masks
@@ -90,7 +97,19 @@ class FastSpeech2Loss(nn.Module):
         total = mel_l + post_l + dur_l + pitch_l + energy_l
         if named_param is not None and self.lambda_f > 0:
             total = total + self.lambda_f * torch.sum(torch.square(named_param))
-        return total, mel_l, post_l, pitch_l, energy_l, dur_l, self.lambda_f
+        return self._with_alignment(align, (total, mel_l, post_l, pitch_l, energy_l, dur_l, self.lambda_f))
+
+    def _with_alignment(self, align, losses):
+        """Learned durations: ``lambda_align * mean_b(nll_b / N_b)`` (the forward-sum loss per token) joins the total
+        and is reported as an eighth entry.  The mean is over this rank's own batch: under data parallelism it equals
+        the full-batch value only for equal per-rank batch sizes."""
+        if align is None:
+            return losses
+        nll = ops.align_forward_sum(align["lp"], align["t_lens"], align["n_lens"])
+        n = align["n_lens"]
+        n = n.to(nll.dtype) if isinstance(n, torch.Tensor) else torch.tensor(n, dtype=nll.dtype, device=nll.device)
+        align_l = (nll / n.to(nll.device)).mean()
+        return (losses[0] + self.lambda_align * align_l,) + tuple(losses[1:]) + (align_l,)
 
 
 def _mse(pred, target, valid, count):

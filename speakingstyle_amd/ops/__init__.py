@@ -418,3 +418,29 @@ def dtw(x, y, x_lens, y_lens, plane_budget=None):
     if use_hip(x):
         return _hip().dtw(x, y, x_lens, y_lens, plane_budget)
     return ref.dtw(x, y, x_lens, y_lens)
+
+
+def align_forward_sum(lp, t_lens, n_lens):
+    """Forward-sum alignment loss (CTC without blanks) over the monotone alignments of a padded batch:
+    lp [B, Tmax, Nmax] fp32, ``t_lens`` / ``n_lens`` the frames / tokens per utterance (host sequences or tensors)
+    -> nll [B], differentiable in lp; see ``ops.reference.align_forward_sum``.  On the GPU one workgroup per
+    utterance for the forward and one for the backward (``csrc/k_align.hip``)."""
+    if use_hip(lp):
+        return _hip().align_forward_sum(lp, t_lens, n_lens)
+    return ref.align_forward_sum(lp, t_lens, n_lens)
+
+
+def align_mas(lp, t_lens, n_lens):
+    """Monotonic alignment search (the Viterbi path of the ``align_forward_sum`` lattice; stay wins ties)
+    -> durations [B, Nmax] int32 that sum to ``t_lens``; see ``ops.reference.align_mas``.  No gradient."""
+    if use_hip(lp):
+        return _hip().align_mas(lp, t_lens, n_lens)
+    return ref.align_mas(lp, t_lens, n_lens)
+
+
+def segment_mean(values, durations):
+    """Mean of each token's run of frames: values [B, Tmax], durations [B, Nmax] -> [B, Nmax] fp32 (0 for a zero
+    duration); see ``ops.reference.segment_mean``."""
+    if use_hip(values):
+        return _hip().segment_mean(values, durations)
+    return ref.segment_mean(values, durations)

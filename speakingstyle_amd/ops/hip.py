@@ -3005,6 +3005,104 @@ def dtw(x, y, x_lens, y_lens, plane_budget=None):
     return cost, path, plen
 
 
+# ------------------------------------------------------------------------ alignment learning (csrc/k_align.hip)
+_SIGS.update({"ssamd_align_fsum_fwd": [P, P, P, I, I, I, I, P, P, P],
+              "ssamd_align_fsum_bwd": [P, P, P, P, P, P, I, I, I, I, P, P],
+              "ssamd_align_mas_plane_words": [I, I, I],
+              "ssamd_align_mas": [P, P, P, I, I, I, I, P, P, P, P],
+              "ssamd_segment_mean": [P, P, I, I, I, P, P]})
+_RESTYPES.update({"ssamd_align_mas_plane_words": L_})
+
+
+def _align_plan(lp, t_lens, n_lens, what):
+    """Validated host lengths -> (t_lens, n_lens int32 on lp's device, waves per workgroup).  Device tensors are
+    used as they are (the checks read their ``host_lengths`` when the loader attached them); host sequences go up
+    in one copy."""
+    tl, nl = ref.align_lens(lp, t_lens, n_lens, what)
+    _need(lp, torch.float32, what + ".lp")
+    if lp.shape[1] * lp.shape[2] >= 2 ** 31:
+        raise ValueError(f"{what}: one utterance's lattice has 32-bit cell offsets")
+    dev = lp.device
+
+    def on_dev(v):
+        return v.to(torch.int32).contiguous() if isinstance(v, torch.Tensor) and v.device == dev else None
+
+    td, nd = on_dev(t_lens), on_dev(n_lens)
+    if td is None or nd is None:
+        host = torch.tensor([tl, nl], dtype=torch.int32)
+        both = (host.pin_memory() if dev.type == "cuda" else host).to(dev, non_blocking=True)
+        td, nd = (both[0] if td is None else td), (both[1] if nd is None else nd)
+    return td, nd, (max(nl) + 63) // 64 if nl else 1
+
+
+class _AlignFsumFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lp, td, nd, W):
+        B, Tmax, Nmax = lp.shape
+        alpha = torch.empty_like(lp)  # written on the lattice cells only; the backward reads only those
+        nll = torch.empty(B, device=lp.device, dtype=torch.float32)
+        rc = lib().ssamd_align_fsum_fwd(_ptr(lp), _ptr(td), _ptr(nd), B, Tmax, Nmax, W, _ptr(alpha), _ptr(nll), _stream())
+        _check(rc, "ssamd_align_fsum_fwd")
+        ctx.save_for_backward(lp, alpha, nll, td, nd)
+        ctx.W = W
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        lp, alpha, nll, td, nd = ctx.saved_tensors
+        B, Tmax, Nmax = lp.shape
+        g = g.float().contiguous()
+        grad = torch.empty_like(lp)  # the kernel writes every cell of every slab
+        rc = lib().ssamd_align_fsum_bwd(_ptr(lp), _ptr(alpha), _ptr(nll), _ptr(g), _ptr(td), _ptr(nd), B, Tmax, Nmax,
+                                        ctx.W, _ptr(grad), _stream())
+        _check(rc, "ssamd_align_fsum_bwd")
+        return grad, None, None, None
+
+
+def align_forward_sum(lp, t_lens, n_lens):
+    """``ops.reference.align_forward_sum`` on the GPU (fp32): one ``align_fwd`` launch, a workgroup per utterance and
+    a wave per 64 tokens, which keeps the alpha plane; the backward is one ``align_fsum_bwd`` launch that writes the
+    whole gradient.  Every utterance comes out bitwise as if alone."""
+    td, nd, W = _align_plan(lp, t_lens, n_lens, "align_forward_sum")
+    if lp.shape[0] == 0:
+        return lp.new_zeros(0)
+    return _AlignFsumFn.apply(lp, td, nd, W)
+
+
+@torch.no_grad()
+def align_mas(lp, t_lens, n_lens):
+    """``ops.reference.align_mas`` on the GPU: the max form of ``align_fwd`` (advance bits as one ballot word per
+    frame and wave, in the stream's workspace) and one wave per utterance that walks them back -> [B, Nmax] int32."""
+    lp = lp.detach()
+    td, nd, W = _align_plan(lp, t_lens, n_lens, "align_mas")
+    B, Tmax, Nmax = lp.shape
+    dur = torch.empty(B, Nmax, device=lp.device, dtype=torch.int32)
+    if B == 0:
+        return dur
+    ws = _workspace(lp.device, 2 * int(lib().ssamd_align_mas_plane_words(B, Tmax, W)))
+    score = torch.empty(B, device=lp.device, dtype=torch.float32)
+    rc = lib().ssamd_align_mas(_ptr(lp), _ptr(td), _ptr(nd), B, Tmax, Nmax, W, _ptr(ws), _ptr(score), _ptr(dur), _stream())
+    _check(rc, "ssamd_align_mas")
+    return dur
+
+
+@torch.no_grad()
+def segment_mean(values, durations):
+    """``ops.reference.segment_mean`` on the GPU: one wave per utterance, a lane per token."""
+    if values.dim() != 2 or durations.dim() != 2 or values.shape[0] != durations.shape[0]:
+        raise ValueError(f"segment_mean: values [B, Tmax] / durations [B, Nmax], got {tuple(values.shape)} / "
+                         f"{tuple(durations.shape)}")
+    v = values.detach().float().contiguous()
+    d = durations.to(torch.int32).contiguous()
+    _need(v, torch.float32, "segment_mean.values")
+    _need(d, torch.int32, "segment_mean.durations")
+    B, Tmax = v.shape
+    out = torch.empty(B, d.shape[1], device=v.device, dtype=torch.float32)
+    rc = lib().ssamd_segment_mean(_ptr(v), _ptr(d), B, Tmax, d.shape[1], _ptr(out), _stream())
+    _check(rc, "ssamd_segment_mean")
+    return out
+
+
 # ------------------------------------------------------------------------ N = 1 heads
 class _HeadFn(torch.autograd.Function):
     """Variance-predictor head Linear(C -> 1) + pad mask (one wave per row)."""

@@ -359,3 +359,160 @@ def dtw(x, y, x_lens, y_lens):
         path[p, :len(cells)] = np.asarray(cells[::-1], dtype=np.int32)
     cost = torch.stack(costs) if P else torch.zeros(0, dtype=x.dtype, device=x.device)
     return cost, torch.from_numpy(path).to(x.device), torch.from_numpy(plen).to(x.device)
+
+
+# ------------------------------------------------- alignment learning (csrc/k_align.hip semantics)
+ALIGN_MAX_N = 1024  # tokens per utterance the kernels cover (16 waves of 64 lanes)
+
+
+def _host_lens(v):
+    if isinstance(v, torch.Tensor):
+        h = getattr(v, "host_lengths", None)
+        v = h if h is not None else v.tolist()
+    return [int(x) for x in v]
+
+
+def align_lens(lp, t_lens, n_lens, what="align"):
+    """Host lengths of a padded alignment batch, validated: lp [B, Tmax, Nmax] with T_b mel frames and N_b tokens per
+    utterance (host sequences, or tensors -- a tensor with a ``host_lengths`` attribute is not read back).  A
+    monotone alignment that visits every token needs 1 <= N_b <= T_b: ``ValueError`` before anything runs."""
+    if lp.dim() != 3:
+        raise ValueError(f"{what}: lp must be [B, Tmax, Nmax], got {tuple(lp.shape)}")
+    tl, nl = _host_lens(t_lens), _host_lens(n_lens)
+    B, Tmax, Nmax = lp.shape
+    if len(tl) != B or len(nl) != B:
+        raise ValueError(f"{what}: {len(tl)} frame lengths / {len(nl)} token lengths for a batch of {B}")
+    if Nmax > ALIGN_MAX_N:
+        raise ValueError(f"{what}: Nmax = {Nmax} exceeds {ALIGN_MAX_N} tokens")
+    for b, (t, n) in enumerate(zip(tl, nl)):
+        if not 1 <= n <= t or t > Tmax or n > Nmax:
+            raise ValueError(f"{what}: utterance {b} has (T, N) = ({t}, {n}) in a [{Tmax}, {Nmax}] lattice; "
+                             "every utterance needs 1 <= N <= T")
+    return tl, nl
+
+
+def _lens_on(v, host, device):
+    if isinstance(v, torch.Tensor) and v.device == device:
+        return v.to(torch.long)
+    return torch.tensor(host, dtype=torch.long, device=device)
+
+
+def _logaddexp(a, b):
+    """max + log1p(exp(-|d|)), -inf where both are -inf (torch.logaddexp's gradient is NaN there; the value is not)."""
+    m = torch.maximum(a, b)
+    r = m + torch.log1p(torch.exp(-(a - b).abs()))
+    return torch.where(m == float("-inf"), m, r)
+
+
+def _shift_tokens(x, fill, back=False):
+    """x[..., n - 1] at n (``back``: x[..., n + 1]), ``fill`` at the open end."""
+    pad = torch.full_like(x[..., :1], fill)
+    return torch.cat([x[..., 1:], pad], -1) if back else torch.cat([pad, x[..., :-1]], -1)
+
+
+def _align_alpha(lp, tl, nl, hard):
+    """alpha [B, Tmax, Nmax] of the lattice (max in place of logaddexp when ``hard``; then also the advance plane
+    [B, Tmax, Nmax] bool: advance only on strict >).  Cells n >= N_b are -inf; rows t >= T_b are not meaningful."""
+    B, Tmax, Nmax = lp.shape
+    ninf = float("-inf")
+    n_idx = torch.arange(Nmax, device=lp.device)
+    lpm = lp.masked_fill((n_idx.unsqueeze(0) >= nl.unsqueeze(1)).unsqueeze(1), ninf)
+    first = torch.full((B, Nmax), ninf, dtype=lp.dtype, device=lp.device)
+    first[:, 0] = 0.0
+    rows, adv = [lpm[:, 0] + first], [torch.zeros(B, Nmax, dtype=torch.bool, device=lp.device)]
+    for t in range(1, Tmax):
+        stay = rows[-1]
+        move = _shift_tokens(stay, ninf)
+        if hard:
+            go = move > stay
+            adv.append(go)
+            rows.append(lpm[:, t] + torch.where(go, move, stay))
+        else:
+            rows.append(lpm[:, t] + _logaddexp(stay, move))
+    return torch.stack(rows, 1), (torch.stack(adv, 1) if hard else None)
+
+
+class _AlignForwardSum(torch.autograd.Function):
+    """The closed-form gradient (the path posterior): autograd through logaddexp is NaN at the -inf cells."""
+
+    @staticmethod
+    def forward(ctx, lp, tl, nl):
+        B = lp.shape[0]
+        alpha, _ = _align_alpha(lp, tl, nl, hard=False)
+        end = alpha[torch.arange(B, device=lp.device), tl - 1, nl - 1]
+        ctx.save_for_backward(lp, alpha, end, tl, nl)
+        return -end
+
+    @staticmethod
+    def backward(ctx, g):
+        lp, alpha, end, tl, nl = ctx.saved_tensors
+        B, Tmax, Nmax = lp.shape
+        ninf = float("-inf")
+        n_idx = torch.arange(Nmax, device=lp.device).unsqueeze(0)
+        lpm = lp.masked_fill((n_idx >= nl.unsqueeze(1)).unsqueeze(1), ninf)
+        last = torch.where(n_idx == (nl - 1).unsqueeze(1), 0.0, ninf).to(lp.dtype)  # beta(T_b - 1, .)
+        none = torch.full_like(last, ninf)
+        rows = [None] * Tmax
+        nxt = none  # lp + beta of frame t + 1
+        for t in range(Tmax - 1, -1, -1):
+            beta = _logaddexp(nxt, _shift_tokens(nxt, ninf, back=True))
+            at = (tl - 1).unsqueeze(1)
+            beta = torch.where(at == t, last, torch.where(at < t, none, beta))
+            rows[t] = beta
+            nxt = lpm[:, t] + beta
+        beta = torch.stack(rows, 1)
+        x = alpha + beta - end.view(B, 1, 1)
+        t_idx = torch.arange(Tmax, device=lp.device).view(1, Tmax, 1)
+        inside = (t_idx < tl.view(B, 1, 1)) & (n_idx.unsqueeze(1) < nl.view(B, 1, 1)) & (x > ninf)
+        post = torch.where(inside, torch.exp(torch.where(inside, x, torch.zeros_like(x))), torch.zeros_like(x))
+        return -post * g.to(lp.dtype).view(B, 1, 1), None, None
+
+
+def align_forward_sum(lp, t_lens, n_lens):
+    """Negative total log-probability of all monotone alignments of T_b frames to N_b tokens: paths start at token 0,
+    end at token N_b - 1 and at each frame stay or advance by one.  This is the CTC forward-sum without blanks.
+
+        alpha(0, 0) = lp(0, 0), alpha(0, n > 0) = -inf
+        alpha(t, n) = lp(t, n) + logaddexp(alpha(t-1, n), alpha(t-1, n-1)),     nll_b = -alpha(T_b - 1, N_b - 1)
+
+    lp [B, Tmax, Nmax] (only cells t < T_b, n < N_b are read) -> nll [B] in lp's dtype (float64 = the oracle),
+    differentiable in lp: the gradient is minus the path posterior exp(alpha + beta - alpha_end), exactly 0 on
+    unreachable cells and on padding."""
+    tl, nl = align_lens(lp, t_lens, n_lens, "align_forward_sum")
+    return _AlignForwardSum.apply(lp, _lens_on(t_lens, tl, lp.device), _lens_on(n_lens, nl, lp.device))
+
+
+@torch.no_grad()
+def align_mas(lp, t_lens, n_lens):
+    """Monotonic alignment search: the best path of the ``align_forward_sum`` lattice (max in place of logaddexp;
+    on a tie stay wins, advance only on strict >), walked back from (T_b - 1, N_b - 1).
+    -> durations [B, Nmax] int32: frames on each token, >= 1 for n < N_b, 0 beyond, summing to T_b."""
+    import numpy as np
+
+    tl, nl = align_lens(lp, t_lens, n_lens, "align_mas")
+    B, Tmax, Nmax = lp.shape
+    _, adv = _align_alpha(lp.detach(), _lens_on(t_lens, tl, lp.device), _lens_on(n_lens, nl, lp.device), hard=True)
+    adv = adv.cpu().numpy()
+    dur = np.zeros((B, Nmax), dtype=np.int32)
+    for b in range(B):
+        n = nl[b] - 1
+        for t in range(tl[b] - 1, -1, -1):
+            dur[b, n] += 1
+            if t > 0 and adv[b, t, n]:
+                n -= 1
+    return torch.from_numpy(dur).to(lp.device)
+
+
+def segment_mean(values, durations):
+    """Mean of each token's run of frames: values [B, Tmax], durations [B, Nmax] (token n of utterance b owns the
+    frames sum(d[:n]) .. sum(d[:n + 1]) - 1) -> [B, Nmax] fp32, 0 for a zero duration
+    (``data/preprocess.py::phoneme_average`` on the device; frames added in order)."""
+    B, Tmax = values.shape
+    Nmax = durations.shape[1]
+    d = durations.to(torch.long).clamp(min=0)
+    ends = torch.cumsum(d, 1)
+    t_idx = torch.arange(Tmax, device=values.device).unsqueeze(0).expand(B, Tmax).contiguous()
+    tok = torch.searchsorted(ends, t_idx, right=True)  # frames past the last run fall into slot Nmax
+    sums = torch.zeros(B, Nmax + 1, dtype=torch.float32, device=values.device)
+    sums.scatter_add_(1, tok, values.float())
+    return torch.where(d > 0, sums[:, :Nmax] / d.clamp(min=1).float(), torch.zeros_like(sums[:, :Nmax]))

@@ -23,7 +23,8 @@ def evaluate(model, step, configs, logger=None, vocoder=None, named_param=None):
                         collate_fn=dataset.collate_fn, num_workers=2)
     loss_fn = FastSpeech2Loss(preprocess_config, train_config)
     device = next(model.parameters()).device
-    sums = torch.zeros(7, dtype=torch.float64, device=device)
+    sums = torch.zeros(8, dtype=torch.float64, device=device)  # 6 loss terms, utterances, alignment loss
+    has_align = False
     batch = output = None
     for batchs in loader:
         for batch in batchs:
@@ -35,11 +36,17 @@ def evaluate(model, step, configs, logger=None, vocoder=None, named_param=None):
             for i in range(6):
                 sums[i] += float(losses[i]) * n
             sums[6] += n
+            if len(losses) > 7:  # learned durations: the forward-sum alignment loss
+                has_align = True
+                sums[7] += float(losses[7]) * n
     if world > 1:
         torch.distributed.all_reduce(sums)
     means = (sums[:6] / sums[6].clamp(min=1)).tolist()
     message = ("Validation Step {}, Total Loss: {:.4f}, Mel Loss: {:.4f}, Mel PostNet Loss: {:.4f}, "
                "Pitch Loss: {:.4f}, Energy Loss: {:.4f}, Duration Loss: {:.4f}").format(step, *means)
+    if has_align:
+        means.append(float(sums[7] / sums[6].clamp(min=1)))
+        message += ", Align Loss: {:.4f}".format(means[6])
     if logger is not None:
         log_scalars(logger, step, losses=means)
         if batch is not None:

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
+from ..config import learned_durations
 from ..data.dataset import Dataset, to_device
 from ..data.synthetic import SyntheticBatches
 from ..parallel import ddp
@@ -54,7 +55,8 @@ def _batches(configs, device, rank, world, synthetic: bool, seed: int, pos=None)
         per_rank = max(1, bs // world)
         gen = SyntheticBatches(per_rank, device=device, max_seq_len=max_len, seed=seed + rank,
                                n_speakers=_n_speakers(preprocess_config), frames_per_batch=budget or None,
-                               frame_level=preprocess_config["preprocessing"]["pitch"]["feature"] == "frame_level")
+                               frame_level=preprocess_config["preprocessing"]["pitch"]["feature"] == "frame_level",
+                               learned_durations=learned_durations(preprocess_config))
         # one group = one batch; every group re-seeds the stream from (seed + rank, group index), so a
         # resume at the checkpoint's data position continues with exactly the batches that were next
         gi = int(pos[1]) if pos else 0
@@ -212,11 +214,13 @@ def train(args, configs):
                     if rank == 0:
                         msg1 = "Step {}/{}, ".format(step, total_step)
                         msg2 = ("Total Loss: {:.4f}, Mel Loss: {:.4f}, Mel PostNet Loss: {:.4f}, Pitch Loss: {:.4f}, "
-                                "Energy Loss: {:.4f}, Duration Loss: {:.4f}").format(*vals)
+                                "Energy Loss: {:.4f}, Duration Loss: {:.4f}").format(*vals[:6])
+                        if len(vals) > 6:  # learned durations
+                            msg2 += ", Align Loss: {:.4f}".format(vals[6])
                         with open(os.path.join(train_log_path, "log.txt"), "a") as f:
                             f.write(msg1 + msg2 + "\n")
                         print(msg1 + msg2, flush=True)
-                        log_scalars(train_logger, step, losses=vals, lr=trainer.last_lr, lambdas=losses[-1])
+                        log_scalars(train_logger, step, losses=vals, lr=trainer.last_lr, lambdas=losses[6])
                         train_logger.add_scalar("Perf/step_ms", 1000.0 * dt / log_step, step)
                         train_logger.add_scalar("Perf/mel_frames_per_s", frames / max(dt, 1e-9), step)
                         train_logger.add_scalar("Perf/skipped_steps", float(trainer.opt.skipped_steps), step)

@@ -135,14 +135,20 @@ class Trainer:
 
         Each rank's masked terms are its share of the global mean (they divide by the
         all-reduced valid counts), so the global value is their SUM over ranks; the
-        ``lambda_f * sum(s^2)`` FiLM term is identical on every rank and is added once."""
-        terms = torch.stack([l.detach().float().reshape(()) for l in losses[1:6]])
+        ``lambda_f * sum(s^2)`` FiLM term is identical on every rank and is added once.
+        Learned durations: the alignment loss (a mean over each rank's own batch) follows as a seventh value,
+        averaged over the ranks."""
+        terms = [l.detach().float().reshape(()) for l in losses[1:6]]
+        has_align = len(losses) > 7
+        if has_align:
+            terms.append(losses[7].detach().float().reshape(()) / self.world)
+        terms = torch.stack(terms)
         if self.world > 1:
             import torch.distributed as dist
 
             dist.all_reduce(terms)
         vals = [float(v) for v in terms]
-        total = sum(vals)
+        total = sum(vals[:5]) + (self.loss_fn.lambda_align * vals[5] if has_align else 0.0)
         named = self.model.film_scalars()
         if named is not None and self.loss_fn.lambda_f > 0:
             total += float(self.loss_fn.lambda_f * torch.sum(torch.square(named.detach().float())))
@@ -219,6 +225,9 @@ class Trainer:
         if self.world > 1 and named is not None and self.loss_fn.lambda_f > 0:
             # the FiLM L2 term is identical on every rank: scale so the SUM all-reduce counts it once
             total = total - (1.0 - 1.0 / self.world) * self.loss_fn.lambda_f * torch.sum(torch.square(named))
+        if self.world > 1 and len(losses) > 7:
+            # the alignment loss is a mean over this rank's batch: the SUM all-reduce then averages the ranks
+            total = total - (1.0 - 1.0 / self.world) * self.loss_fn.lambda_align * losses[7]
         tm.phase("backward")
         ht = self._host_tail
         if ht is not None:

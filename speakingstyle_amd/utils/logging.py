@@ -16,7 +16,8 @@ def log_scalars(logger, step=None, losses=None, lr=None, lambdas=None, fig=None,
     if logger is None:
         return
     if losses is not None:
-        names = ["total_loss", "mel_loss", "mel_postnet_loss", "pitch_loss", "energy_loss", "duration_loss"]
+        names = ["total_loss", "mel_loss", "mel_postnet_loss", "pitch_loss", "energy_loss", "duration_loss",
+                 "align_loss"]  # the last one only with learned durations (zip stops at the shorter list)
         for n, v in zip(names, losses):
             logger.add_scalar(f"Loss/{n}", float(v), step)
     if lr is not None:
@@ -83,10 +84,14 @@ def synth_one_sample(targets, predictions, vocoder, model_config, preprocess_con
     mel_len = min(mel_len, predictions[1].shape[1])
     mel_target = targets[6][0, :mel_len].detach().float().transpose(0, 1)
     mel_pred = predictions[1][0, :mel_len].detach().float().transpose(0, 1)
-    dur = targets[11][0, :src_len].detach().cpu().numpy()
+    # learned durations: the batch has none; the model's output carries its MAS durations and derived targets
+    align = predictions[10] if len(predictions) > 10 else None
+    d_t, p_t, e_t = ((align["durations"], align["p_targets"], align["e_targets"]) if align is not None
+                     else (targets[11], targets[9], targets[10]))
+    dur = d_t[0, :src_len].detach().cpu().numpy()
     pp = preprocess_config["preprocessing"]
-    pitch = targets[9][0, : (src_len if pp["pitch"]["feature"] == "phoneme_level" else mel_len)].detach().cpu().numpy()
-    energy = targets[10][0, : (src_len if pp["energy"]["feature"] == "phoneme_level" else mel_len)].detach().cpu().numpy()
+    pitch = p_t[0, : (src_len if pp["pitch"]["feature"] == "phoneme_level" else mel_len)].detach().cpu().numpy()
+    energy = e_t[0, : (src_len if pp["energy"]["feature"] == "phoneme_level" else mel_len)].detach().cpu().numpy()
     pitch = _feature_curve(pitch, dur, pp["pitch"]["feature"])
     energy = _feature_curve(energy, dur, pp["energy"]["feature"])
     fig = None

@@ -3,7 +3,7 @@
 
 Reports achieved TFLOP/s (GEMM-shaped) or GB/s (memory-bound) per kernel, and
 the hipBLASLt number for the plain-GEMM equivalent (torch.matmul) as a yardstick.
-Usage (GPU box): python tools/bench_kernels.py [--rows 160000] [--iters 20] | --griffin-lim | --dtw
+Usage (GPU box): python tools/bench_kernels.py [--rows 160000] [--iters 20] | --griffin-lim | --dtw | --align
 """
 import argparse
 import json
@@ -184,6 +184,123 @@ def bench_dtw(out_path, rounds=3):
             f.write(text)
 
 
+def align_workload(batch=200):
+    """(lp [B, Tmax, Nmax] on the CPU, t_lens, n_lens): ``batch`` utterances with the LJSpeech ``val.txt`` phoneme
+    counts and 8.1 frames per phoneme on average (as data/synthetic.py draws them); lp = log_softmax(3 randn) over
+    each utterance's own tokens."""
+    import numpy as np
+
+    from speakingstyle_amd.data import synthetic
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    counts = synthetic.ljspeech_phone_counts(os.path.join(root, "preprocessed_data", "LJSpeech", "val.txt"))
+    rng = np.random.default_rng(0)
+    nl = rng.choice(counts, size=batch).astype(np.int64)
+    tl = np.clip(np.round(nl * rng.normal(8.1, 0.8, size=batch)), nl, 1000).astype(np.int64)
+    g = torch.Generator().manual_seed(batch)
+    lp = 3.0 * torch.randn(batch, int(tl.max()), int(nl.max()), generator=g)
+    pad = torch.arange(int(nl.max())).view(1, 1, -1) >= torch.from_numpy(nl).view(-1, 1, 1)
+    return torch.log_softmax(lp.masked_fill(pad, float("-inf")), -1), tl.tolist(), nl.tolist()
+
+
+def bench_align(out_path, rounds=3):
+    """``ops.align_forward_sum`` forward + backward and ``ops.align_mas`` (csrc/k_align.hip) against the torch
+    reference loop of ``ops/reference.py`` and, for the forward-sum, ``F.ctc_loss`` forward + backward on the same
+    lattice size, all on the same GPU tensors.  The arms alternate in one process; every call is timed wall-clock
+    between two device synchronisations.  The kernels are also timed on their own with device events."""
+    import time
+
+    import torch.nn.functional as F
+
+    from speakingstyle_amd import ops
+    from speakingstyle_amd.ops import reference as ref
+
+    dev = torch.device("cuda")
+    lp, tl, nl = align_workload()
+    lp = lp.to(dev)
+    B, Tmax, Nmax = lp.shape
+    cells = sum(a * b for a, b in zip(tl, nl))
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    def fsum(fn):
+        x = lp.detach().requires_grad_(True)
+        fn(x, tl, nl).sum().backward()
+        return x.grad
+
+    # the CTC yardstick: same [T, B, N + 1] lattice size, targets 1..N_b (blank 0 unused by the labels)
+    ctc_lp = torch.log_softmax(torch.randn(Tmax, B, Nmax + 1, device=dev), -1)
+    ctc_tg = torch.arange(1, Nmax + 1, device=dev).unsqueeze(0).repeat(B, 1)
+    ctc_tl, ctc_nl = torch.tensor(tl, device=dev), torch.tensor(nl, device=dev)
+
+    def ctc():
+        x = ctc_lp.detach().requires_grad_(True)
+        F.ctc_loss(x, ctc_tg, ctc_tl, ctc_nl, reduction="sum").backward()
+
+    arms = [("forward-sum fwd + bwd", "hip ops.align_forward_sum", lambda: fsum(ops.align_forward_sum)),
+            ("forward-sum fwd + bwd", "torch reference loop", lambda: fsum(ref.align_forward_sum)),
+            ("forward-sum fwd + bwd", "F.ctc_loss fwd + bwd", ctc),
+            ("MAS durations", "hip ops.align_mas", lambda: ops.align_mas(lp, tl, nl)),
+            ("MAS durations", "torch reference loop", lambda: ref.align_mas(lp, tl, nl))]
+    t = {a[:2]: [] for a in arms}
+    for r in range(rounds + 1):
+        for what, arm, fn in arms:
+            ms = wall(fn)
+            if r >= 1:
+                t[(what, arm)].append(ms)
+    lines = [f"Alignment learning kernels, fp32, {torch.cuda.get_device_name(0)}",
+             f"batch {B}, LJSpeech val.txt phoneme counts (mean {sum(nl) / B:.0f}, max {max(nl)}), "
+             f"{sum(tl) / sum(nl):.1f} frames per phoneme: lattice [{B}, {Tmax}, {Nmax}], {cells} cells inside "
+             f"({cells * 4 / 1e6:.1f} MB of lp)",
+             f"{rounds} alternating rounds per arm after 1 warm-up round; wall time per call between device syncs (ms);",
+             "kernel rows: device-event time of one launch (3 warm-up launches before each), 20 samples", "",
+             f"{'workload':24s} {'arm':>28s} {'median':>10s} {'min':>10s} {'max':>10s}"]
+    med = {}
+    for (what, arm), v in t.items():
+        v.sort()
+        med[(what, arm)] = v[len(v) // 2]
+        lines.append(f"{what:24s} {arm:>28s} {v[len(v) // 2]:10.3f} {v[0]:10.3f} {v[-1]:10.3f}")
+    f_hip = med[("forward-sum fwd + bwd", "hip ops.align_forward_sum")]
+    lines.append(f"{'':24s} {'torch loop / hip (medians)':>28s} "
+                 f"{med[('forward-sum fwd + bwd', 'torch reference loop')] / f_hip:10.1f}")
+    lines.append(f"{'':24s} {'ctc_loss / hip (medians)':>28s} "
+                 f"{med[('forward-sum fwd + bwd', 'F.ctc_loss fwd + bwd')] / f_hip:10.1f}")
+    lines.append(f"{'':24s} {'MAS torch loop / hip':>28s} "
+                 f"{med[('MAS durations', 'torch reference loop')] / med[('MAS durations', 'hip ops.align_mas')]:10.1f}")
+    # the kernels alone
+    td, nd, W = hip._align_plan(lp, tl, nl, "bench")
+    alpha, grad = torch.empty_like(lp), torch.empty_like(lp)
+    nll, gn = torch.empty(B, device=dev), torch.ones(B, device=dev)
+    dur = torch.empty(B, Nmax, device=dev, dtype=torch.int32)
+    ws = hip._workspace(dev, 2 * int(hip.lib().ssamd_align_mas_plane_words(B, Tmax, W)))
+    L, P, S = hip.lib(), hip._ptr, hip._stream
+    kernels = [("align_fwd (sum) kernel", 2, lambda: L.ssamd_align_fsum_fwd(P(lp), P(td), P(nd), B, Tmax, Nmax, W, P(alpha), P(nll), S())),
+               ("align_fsum_bwd kernel", 3, lambda: L.ssamd_align_fsum_bwd(P(lp), P(alpha), P(nll), P(gn), P(td), P(nd), B, Tmax, Nmax, W, P(grad), S())),
+               ("align_fwd (max) + path", 1, lambda: L.ssamd_align_mas(P(lp), P(td), P(nd), B, Tmax, Nmax, W, P(ws), P(nll), P(dur), S()))]
+    lines += ["", f"{'kernel':24s} {'':>28s} {'median':>10s} {'min':>10s} {'max':>10s} {'GB/s':>8s} {'% of 8 TB/s':>12s}"]
+    for name, planes, fn in kernels:
+        v = sorted(timeit(fn, 1) for _ in range(20))
+        # traffic that has to move: `planes` fp32 planes over the cells inside the lattices (the backward also zeroes
+        # the padding of its slab, counted with the full slab)
+        moved = (planes - 1) * cells * 4 + (B * Tmax * Nmax * 4 if "bwd" in name else cells * 4)
+        gbs = moved / (v[len(v) // 2] * 1e-3) / 1e9
+        lines.append(f"{name:24s} {'':>28s} {v[len(v) // 2]:10.3f} {v[0]:10.3f} {v[-1]:10.3f} {gbs:8.0f} {100 * gbs / 8000:11.1f}%")
+    lines += ["", "The recurrences are latency-bound, not bandwidth-bound: a wave advances one frame per ~2 transcendental",
+              "round trips and an utterance occupies ceil(N / 64) waves, so the batch keeps a few hundred waves of the",
+              "chip busy; the last column says how far that is from moving the same planes at HBM speed."]
+    text = "\n".join(lines) + "\n"
+    print(text, end="", flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=160000)
@@ -193,9 +310,14 @@ def main():
                     help="only the Griffin-Lim arm: HIP kernels vs the torch loop, table written to --out")
     ap.add_argument("--dtw", action="store_true",
                     help="only the DTW arm: HIP kernels vs the torch wavefront, table written to --out")
-    ap.add_argument("--out", default=None, help="default: profiles/griffin_lim.txt, profiles/dtw.txt")
+    ap.add_argument("--align", action="store_true",
+                    help="only the alignment arm: forward-sum / MAS kernels vs the torch loop and F.ctc_loss")
+    ap.add_argument("--out", default=None,
+                    help="default: profiles/griffin_lim.txt, profiles/dtw.txt, profiles/align.txt")
     args = ap.parse_args()
     prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    if args.align:
+        return bench_align(args.out or os.path.join(prof, "align.txt"))
     if args.dtw:
         return bench_dtw(args.out or os.path.join(prof, "dtw.txt"))
     args.out = args.out or os.path.join(prof, "griffin_lim.txt")

@@ -97,6 +97,13 @@ SETS = {
 }
 SETS["LJSpeech"][0]["path"]["preprocessed_path"] = "./preprocessed_data/LJSpeech"
 SETS["LJSpeech_paper"][0]["path"]["raw_path"] = "./raw_data/LJSpeech"  # shares LJSpeech's aligned corpus
+# LJSpeech from wavs and transcripts alone: no TextGrids; durations come from the alignment learner
+# (models/aligner.py) trained with the forward-sum loss
+SETS["LJSpeech_unaligned"] = (preprocess("LJSpeech_unaligned"), model(), train("LJSpeech_unaligned", 200, save=1000))
+SETS["LJSpeech_unaligned"][0]["path"]["raw_path"] = "./raw_data/LJSpeech"
+SETS["LJSpeech_unaligned"][0]["preprocessing"]["duration"] = {"source": "learned"}
+SETS["LJSpeech_unaligned"][1]["aligner"] = {"hidden": 128, "temperature": 0.0005, "prior_scaling": 1.0}
+SETS["LJSpeech_unaligned"][2]["loss"] = {"lambda_align": 1.0}
 
 if __name__ == "__main__":
     for name, trip in SETS.items():
