@@ -9,6 +9,7 @@
   objective metrics of free-running synthesis against the recordings (MCD, F0 / energy error along a DTW path):
     python analyze.py objective --restore_step 900000 -p P -m M -t T [--source val.txt] [--out_dir analysis]
         [--pitch_control 1 --energy_control 1 --duration_control 1] [--n_ceps 13] [--batch_size 32] [--cpu]
+        [--wave [--vocoder griffin_lim]]   (pitch and MCD of the vocoded audio against the recordings)
 """
 import argparse
 import json
@@ -34,6 +35,12 @@ def main(argv=None):
     ap.add_argument("--outlier_k", type=float, default=3.0)
     ap.add_argument("--batch_size", type=int, default=None, help="default: 8 (variance), 32 (objective)")
     ap.add_argument("--n_ceps", type=int, default=13, help="objective: mel cepstra 1 .. n_ceps enter the MCD")
+    ap.add_argument("--wave", action="store_true",
+                    help="objective: also vocode every synthesis and compare it with the recording "
+                         "(<raw_path>/<speaker>/<basename>.wav): wave_mcd_db, wave_vde, wave_gpe, wave_ffe, "
+                         "wave_f0_rmse_cents")
+    ap.add_argument("--vocoder", choices=["griffin_lim", "hifigan"], default=None,
+                    help="objective --wave: the vocoder (default: the model config's; griffin_lim needs no checkpoint)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--cpu", action="store_true")
     a = ap.parse_args(argv)
@@ -58,7 +65,7 @@ def main(argv=None):
 
         src = a.source or os.path.join(configs[0]["path"]["preprocessed_path"], "val.txt")
         rep = evaluate_objective(model, configs, src, dev, (a.pitch_control, a.energy_control, a.duration_control),
-                                 a.batch_size or 32, a.out_dir, a.n_ceps)
+                                 a.batch_size or 32, a.out_dir, a.n_ceps, wave=a.wave, vocoder=a.vocoder)
     else:
         from speakingstyle_amd.analysis.inspect import inspect_batch
 

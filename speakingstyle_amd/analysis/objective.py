@@ -15,6 +15,18 @@ wavefront of ``ops.reference`` on the CPU):
 
 The x side of every alignment is the synthesis, the y side the recording.  A synthesis of zero frames has no
 alignment: its path metrics are nan, it is counted in ``n_empty`` and left out of the means and medians.
+
+Waveform-level figures (``wave_metrics``, ``evaluate_objective(wave=True)``): the figures above compare what the model
+predicts; these compare what is heard.  Both waveforms -- the vocoded synthesis and the recording -- go through the
+same front end (log-mel -> cepstra -> ``ops.dtw``) and the same pitch tracker (``ops.yin``: one HIP workgroup per
+frame on the GPU), and the F0 tracks are gathered along the path (Skerry-Ryan et al. 2018, after Chu & Alwan 2009):
+
+  wave_mcd_db         ``mcd_db`` of the audio
+  wave_vde            voicing decision error: share of path cells voiced on one side only
+  wave_gpe            gross pitch error: among cells voiced on both sides, the share with |fa - fb| > 0.2 fb (nan
+                      when there are none)
+  wave_ffe            F0 frame error: share of cells with either error
+  wave_f0_rmse_cents  RMSE of 1200 log2(fa / fb) over the cells voiced on both sides (nan when there are none)
 """
 from __future__ import annotations
 
@@ -32,6 +44,8 @@ from .variance import _stats
 
 MCD_SCALE = 10.0 * math.sqrt(2.0) / math.log(10.0)
 METRICS = ("mcd_db", "logmel_l1", "pitch_rmse", "energy_rmse", "pitch_corr", "dur_mae_frames", "len_ratio")
+WAVE_METRICS = ("wave_mcd_db", "wave_vde", "wave_gpe", "wave_ffe", "wave_f0_rmse_cents")
+GROSS_PITCH_ERROR = 0.2  # relative F0 deviation from the y side that counts as gross
 
 
 def dct_matrix(n_mel: int, n_ceps: int, device=None, dtype=torch.float32) -> torch.Tensor:
@@ -117,6 +131,114 @@ def utterance_metrics(pred_mel, pred_lens, true_mel, true_lens, pred_pitch=None,
     return res
 
 
+def prosody_errors(fa, fb, mask) -> Dict[str, torch.Tensor]:
+    """Voicing / pitch errors of F0 tracks gathered along alignment paths: ``fa`` / ``fb`` [P, L] in Hz (0 =
+    unvoiced; b is the side the deviation is relative to), ``mask`` [P, L] the real cells.  -> float64 [P] each of
+    ``vde``, ``gpe``, ``ffe`` and ``f0_rmse_cents``."""
+    fa, fb = fa.double(), fb.double()
+    n = mask.sum(1).double()
+    va, vb = (fa > 0) & mask, (fb > 0) & mask
+    voicing = va != vb
+    both = va & vb
+    gross = both & ((fa - fb).abs() > GROSS_PITCH_ERROR * fb)
+    nb = both.sum(1).double()
+    nan = torch.full_like(n, float("nan"))
+    one = torch.ones_like(fa)
+    cents = (1200.0 * torch.log2(torch.where(both, fa, one) / torch.where(both, fb, one)))
+    some = nb > 0
+    nb1 = torch.where(some, nb, torch.ones_like(nb))
+    return {"vde": voicing.sum(1).double() / n,
+            "gpe": torch.where(some, gross.sum(1).double() / nb1, nan),
+            "ffe": (voicing | gross).sum(1).double() / n,
+            "f0_rmse_cents": torch.where(some, torch.sqrt((cents * cents).sum(1) / nb1), nan)}
+
+
+_front_ends = {}
+
+
+def _front_end(pp):
+    """The mel front end of a preprocess config (one ``TacotronSTFT`` per setting)."""
+    from ..audio.stft import TacotronSTFT
+
+    pre = pp["preprocessing"]
+    s, m = pre["stft"], pre["mel"]
+    key = (s["filter_length"], s["hop_length"], s["win_length"], m["n_mel_channels"], pre["audio"]["sampling_rate"],
+           m["mel_fmin"], m["mel_fmax"])
+    if key not in _front_ends:
+        _front_ends[key] = TacotronSTFT(*key)
+    return _front_ends[key]
+
+
+def _logmel_rows(wav, lens, stft):
+    """Packed waveforms -> packed log-mel rows [R, n_mel] (1 + N // hop per utterance), one front-end call per
+    utterance (on the GPU the fused log-mel kernel)."""
+    rows, at = [], 0
+    for n in lens:
+        mel, _ = stft.mel_spectrogram(wav[at:at + n].unsqueeze(0))
+        rows.append(mel[0].transpose(0, 1))
+        at += n
+    return torch.cat(rows).contiguous()
+
+
+@torch.no_grad()
+def wave_metrics(wav_a, lens_a, wav_b, lens_b, pp, n_ceps: int = 13, frame: int = 1024) -> Dict[str, np.ndarray]:
+    """Waveform-level metrics of P pairs of utterances: ``wav_a`` / ``wav_b`` packed fp32 samples in [-1, 1] on one
+    device (all utterances back to back) with host sample counts ``lens_a`` / ``lens_b``; ``pp`` the preprocess
+    config (sampling rate, STFT, mel).  Log-mel of both sides -> cepstra -> ``ops.dtw``; ``ops.yin`` (``frame``
+    samples per analysis frame) on both sides; F0 gathered along the path.  a is the x side of the alignment, b the
+    y side and the pitch reference.  -> {metric of ``WAVE_METRICS``: float64 [P]} plus ``path_len``."""
+    lens_a, lens_b = [int(v) for v in lens_a], [int(v) for v in lens_b]
+    pre = pp["preprocessing"]
+    sr, hop = pre["audio"]["sampling_rate"], pre["stft"]["hop_length"]
+    wav_a, wav_b = wav_a.float().contiguous(), wav_b.float().contiguous()
+    fa, frames_a = ops.yin(wav_a, lens_a, sr, hop, frame)  # also checks the lengths before anything else runs
+    fb, frames_b = ops.yin(wav_b, lens_b, sr, hop, frame)
+    stft = _front_end(pp)
+    mel_a, mel_b = _logmel_rows(wav_a, lens_a, stft), _logmel_rows(wav_b, lens_b, stft)
+    cost, path, plen = align(mel_a, frames_a, mel_b, frames_b, n_ceps)
+    ia, ib, mask = _along(path, plen, frames_a, frames_b)
+    err = prosody_errors(fa[ia], fb[ib], mask)
+    out = {"wave_mcd_db": MCD_SCALE * cost.double() / plen.double(), "wave_vde": err["vde"], "wave_gpe": err["gpe"],
+           "wave_ffe": err["ffe"], "wave_f0_rmse_cents": err["f0_rmse_cents"]}
+    res = {k: v.cpu().numpy() for k, v in out.items()}
+    res["path_len"] = plen.cpu().numpy()
+    return res
+
+
+def _recording(pp, spk: str, base: str) -> str:
+    fn = os.path.join(pp["path"]["raw_path"], spk, f"{base}.wav")
+    if not os.path.exists(fn):
+        raise FileNotFoundError(f"waveform-level objective evaluation needs the recording of every listed utterance: "
+                                f"{fn} is missing")
+    return fn
+
+
+def _get_vocoder(vocoder, configs, device):
+    """``vocoder``: None = the configured one, "griffin_lim" / "hifigan" = that one, or a vocoder object."""
+    if vocoder is not None and not isinstance(vocoder, str):
+        return vocoder
+    from ..utils.model import get_vocoder
+
+    mc = configs[1]
+    if vocoder is not None:
+        names = {"griffin_lim": "GriffinLim", "hifigan": "HiFi-GAN"}
+        if vocoder not in names:
+            raise ValueError(f"vocoder {vocoder!r} not supported ({', '.join(names)})")
+        mc = dict(mc, vocoder=dict(mc["vocoder"], model=names[vocoder]))
+    return get_vocoder(mc, device, preprocess_config=configs[0])
+
+
+def _vocode(vocoder, mel, frames, hop):
+    """Synthesized mels [B, Tmax, n_mel] with host frame counts -> one fp32 waveform per utterance, on the mels'
+    device.  Griffin-Lim returns hop * (T - 1) samples of an utterance of T frames, a generator T * hop."""
+    from ..models.griffinlim import GriffinLim
+
+    x = mel.to(getattr(vocoder, "mel_dtype", torch.bfloat16) if mel.is_cuda else torch.float32).contiguous()
+    wav = vocoder.infer(x, lengths=frames).float().clamp(-1.0, 1.0)  # as written to a file
+    short = hop if isinstance(vocoder, GriffinLim) else 0
+    return [wav[i, :max(0, hop * T - short)] for i, T in enumerate(frames)]
+
+
 def _load(root: str, kind: str, spk: str, base: str) -> np.ndarray:
     fn = os.path.join(root, kind, f"{spk}-{kind}-{base}.npy")
     if not os.path.exists(fn):
@@ -136,9 +258,9 @@ def _frames(values: np.ndarray, durations: np.ndarray, level: str, T: int, what:
     return v[:T]
 
 
-def _summary(rows: List[dict]) -> Dict:
+def _summary(rows: List[dict], metrics=METRICS) -> Dict:
     out = {"n": len(rows), "n_empty": sum(1 for r in rows if r["pred_frames"] == 0), "mean": {}, "median": {}}
-    for m in METRICS:
+    for m in metrics:
         v = np.asarray([r[m] for r in rows], np.float64)
         v = v[~np.isnan(v)]
         out["mean"][m] = float(v.mean()) if v.size else float("nan")
@@ -148,11 +270,16 @@ def _summary(rows: List[dict]) -> Dict:
 
 @torch.no_grad()
 def evaluate_objective(model, configs, source: str, device, controls=(1.0, 1.0, 1.0), batch_size: int = 32,
-                       out_dir: Optional[str] = None, n_ceps: int = 13) -> Dict:
+                       out_dir: Optional[str] = None, n_ceps: int = 13, wave: bool = False, vocoder=None) -> Dict:
     """Free-running synthesis (no targets, predicted durations) of every utterance of ``source`` (a ``val.txt``-style
     list) against its stored mel / pitch / energy / duration; one ``ops.dtw`` call per batch of pairs.
     -> {"n", "n_empty", "mean": {metric: value}, "median": {...}}; with ``out_dir`` also ``objective_summary.json``
-    and the per-utterance ``objective.csv``."""
+    and the per-utterance ``objective.csv``.
+
+    ``wave``: also the waveform-level ``WAVE_METRICS`` -- every synthesized mel is vocoded (``vocoder``: None = the
+    configured one, ``"griffin_lim"`` needs no checkpoint, ``"hifigan"``, or a vocoder object) and compared with the
+    recording ``<raw_path>/<speaker>/<basename>.wav`` at the configured rate (``wave_metrics``).  A synthesis too
+    short for the pitch tracker's frame has nan there."""
     from torch.utils.data import DataLoader
 
     from ..data.dataset import TextDataset, to_device
@@ -167,10 +294,17 @@ def evaluate_objective(model, configs, source: str, device, controls=(1.0, 1.0, 
     speaker_of = dict(zip(ds.basename, ds.speaker))
     dev = torch.device(device)
     model.eval()
+    if wave:
+        from ..audio.io import read_wav
+
+        voc = _get_vocoder(vocoder, configs, dev)
+        sr, hop = pp["preprocessing"]["audio"]["sampling_rate"], pp["preprocessing"]["stft"]["hop_length"]
+        yin_frame = 1024
     rows: List[dict] = []
     for batch in DataLoader(ds, batch_size=batch_size, collate_fn=ds.collate_fn):
         names = batch[0]
         truth = []
+        recs = [_recording(pp, speaker_of[base], base) for base in names] if wave else []
         for base in names:  # fail on a missing file before the model runs
             spk = speaker_of[base]
             dur = _load(root, "duration", spk, base).astype(np.int64).reshape(-1)
@@ -205,6 +339,20 @@ def evaluate_objective(model, configs, source: str, device, controls=(1.0, 1.0, 
                 torch.from_numpy(np.concatenate([truth[i][0] for i in keep])).to(dev), [truth[i][0].shape[0] for i in keep],
                 f64(pred_con["pitch"]), f64([truth[i][1] for i in keep]), f64(pred_con["energy"]),
                 f64([truth[i][2] for i in keep]), [pred_dur[i] for i in keep], [truth[i][3] for i in keep], n_ceps)
+        wres, wat = {}, {}
+        if wave:
+            syn = dict(zip(keep, _vocode(voc, post[keep], [int(mel_lens[i]) for i in keep], hop))) if keep else {}
+            rec = {}
+            for i in keep:
+                y = np.clip(read_wav(recs[i], sr)[0], -1.0, 1.0)
+                if syn[i].shape[0] > yin_frame // 2 and y.shape[0] > yin_frame // 2:
+                    rec[i] = torch.from_numpy(y).to(dev)
+            wkeep = list(rec)
+            wat = {i: k for k, i in enumerate(wkeep)}
+            if wkeep:
+                wres = wave_metrics(torch.cat([syn[i] for i in wkeep]), [syn[i].shape[0] for i in wkeep],
+                                    torch.cat([rec[i] for i in wkeep]), [rec[i].shape[0] for i in wkeep], pp, n_ceps,
+                                    yin_frame)
         at = {i: k for k, i in enumerate(keep)}
         for i, base in enumerate(names):
             row = {"basename": base, "pred_frames": int(mel_lens[i]), "true_frames": int(truth[i][0].shape[0])}
@@ -214,8 +362,10 @@ def evaluate_objective(model, configs, source: str, device, controls=(1.0, 1.0, 
                 row["dur_mae_frames"] = float(np.abs(pred_dur[i] - truth[i][3]).mean())
                 row["len_ratio"] = 0.0
             row["path_len"] = int(res["path_len"][at[i]]) if i in at else 0
+            for m in WAVE_METRICS if wave else ():
+                row[m] = float(wres[m][wat[i]]) if i in wat else float("nan")
             rows.append(row)
-    summary = _summary(rows)
+    summary = _summary(rows, METRICS + WAVE_METRICS if wave else METRICS)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "objective_summary.json"), "w") as f:

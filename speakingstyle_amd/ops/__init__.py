@@ -420,6 +420,15 @@ def dtw(x, y, x_lens, y_lens, plane_budget=None):
     return ref.dtw(x, y, x_lens, y_lens)
 
 
+def yin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, threshold=0.15, return_cmnd=False):
+    """YIN fundamental frequency of packed utterances (``wav`` one fp32 vector of all samples back to back, host
+    sample counts ``lengths``) -> (f0 [R] over the packed frame rows, 1 + N_b // hop per utterance; those frame
+    counts as a host list[; the cmnd plane [R, tau_max + 1]]); see ``ops.reference.yin``.  On the GPU one workgroup
+    per frame row (``csrc/k_pitch.hip``)."""
+    fn = _hip().yin if use_hip(wav) else ref.yin
+    return fn(wav, lengths, sr, hop, frame, fmin, fmax, threshold, return_cmnd)
+
+
 def align_forward_sum(lp, t_lens, n_lens):
     """Forward-sum alignment loss (CTC without blanks) over the monotone alignments of a padded batch:
     lp [B, Tmax, Nmax] fp32, ``t_lens`` / ``n_lens`` the frames / tokens per utterance (host sequences or tensors)

@@ -3005,6 +3005,49 @@ def dtw(x, y, x_lens, y_lens, plane_budget=None):
     return cost, path, plen
 
 
+# ------------------------------------------------------------------------ YIN pitch tracker (csrc/k_pitch.hip)
+_SIGS.update({"ssamd_yin": [P, P, P, P, I, I, I, I, I, F, F, P, P, P]})
+
+
+class YinPack:
+    """Device tables of a packed YIN batch, built from the host lengths and uploaded in one copy: ``off`` int64 [B]
+    (viewed as int32 pairs) first sample of every utterance, ``n`` int32 [B] its samples, ``rows`` int32 [R, 2] =
+    {utterance, local frame} per packed frame row."""
+
+    def __init__(self, lens, frames, device):
+        import numpy as np
+
+        lens, frames = np.asarray(lens, dtype=np.int64), np.asarray(frames, dtype=np.int64)
+        self.B, self.R = len(lens), int(frames.sum())
+        assert self.R < 2 ** 31, "packed YIN: too many frame rows"
+        off = np.zeros(self.B, dtype=np.int64)
+        off[1:] = np.cumsum(lens)[:-1]
+        cu = np.zeros(self.B, dtype=np.int64)
+        cu[1:] = np.cumsum(frames)[:-1]
+        u = np.repeat(np.arange(self.B), frames)
+        rows = np.stack([u, np.arange(self.R) - cu[u]], axis=1).astype(np.int32)
+        host = torch.from_numpy(np.concatenate([off.view(np.int32), lens.astype(np.int32), rows.reshape(-1)]))
+        self.buf = (host.pin_memory() if device.type == "cuda" else host).to(device, non_blocking=True)
+        self.off, self.n, self.rows = self.buf[:2 * self.B], self.buf[2 * self.B:3 * self.B], self.buf[3 * self.B:]
+
+
+def yin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, threshold=0.15, return_cmnd=False):
+    """``ops.reference.yin`` on the GPU (fp32): one ``yin_kernel`` launch for the whole mixed-length batch, a
+    workgroup per packed frame row; every utterance comes out bitwise as if alone.  ``lengths`` is a host sequence:
+    nothing here waits for the device.  -> f0 [R] fp32, the per-utterance frame counts (host list) and, with
+    ``return_cmnd``, the cmnd plane [R, tau_max + 1] fp32."""
+    lens, frames, tau_min, tau_max = ref.yin_plan(wav, lengths, sr, hop, frame, fmin, fmax)
+    _need(wav, torch.float32, "yin.wav")
+    dev = wav.device
+    pack = YinPack(lens, frames, dev)
+    f0 = torch.empty(pack.R, device=dev, dtype=torch.float32)
+    cm = torch.empty(pack.R, tau_max + 1, device=dev, dtype=torch.float32) if return_cmnd else None
+    rc = lib().ssamd_yin(_ptr(wav), _ptr(pack.off), _ptr(pack.n), _ptr(pack.rows), pack.R, int(hop), int(frame),
+                         tau_min, tau_max, float(sr), float(threshold), _ptr(f0), _ptr(cm), _stream())
+    _check(rc, "ssamd_yin")
+    return (f0, frames, cm) if return_cmnd else (f0, frames)
+
+
 # ------------------------------------------------------------------------ alignment learning (csrc/k_align.hip)
 _SIGS.update({"ssamd_align_fsum_fwd": [P, P, P, I, I, I, I, P, P, P],
               "ssamd_align_fsum_bwd": [P, P, P, P, P, P, I, I, I, I, P, P],

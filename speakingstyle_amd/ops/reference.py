@@ -516,3 +516,95 @@ def segment_mean(values, durations):
     sums = torch.zeros(B, Nmax + 1, dtype=torch.float32, device=values.device)
     sums.scatter_add_(1, tok, values.float())
     return torch.where(d > 0, sums[:, :Nmax] / d.clamp(min=1).float(), torch.zeros_like(sums[:, :Nmax]))
+
+
+# ------------------------------------------------------------------ YIN pitch tracker (csrc/k_pitch.hip semantics)
+def yin_plan(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0):
+    """Host side of a packed YIN batch, validated: -> (sample counts, frame counts 1 + N // hop, tau_min, tau_max).
+    ``ValueError`` with the offending value for a frame size the kernel does not cover, a hop outside 1 .. frame,
+    an utterance too short for the reflect padding (N <= frame / 2) or lengths that do not add up."""
+    frame, hop = int(frame), int(hop)
+    if frame not in (512, 1024, 2048):
+        raise ValueError(f"yin: frame {frame} not covered (512, 1024 or 2048)")
+    if not 0 < hop <= frame:
+        raise ValueError(f"yin: hop {hop} must lie in 1 .. frame = {frame}")
+    lens = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    if wav.dim() != 1:
+        raise ValueError(f"yin: wav must be one packed vector of samples, got shape {tuple(wav.shape)}")
+    for b, n in enumerate(lens):
+        if n <= frame // 2:
+            raise ValueError(f"yin: utterance {b} has {n} samples; reflect padding needs more than frame / 2 = "
+                             f"{frame // 2}")
+        if n + frame >= 2 ** 31:
+            raise ValueError(f"yin: utterance {b} has {n} samples; positions inside an utterance are 32-bit")
+    if sum(lens) != wav.shape[0]:
+        raise ValueError(f"yin: lengths sum to {sum(lens)} but wav has {wav.shape[0]} samples")
+    tau_min = max(2, int(sr / fmax))
+    tau_max = min(frame // 2, int(sr / fmin) + 1)
+    if tau_min >= tau_max:
+        raise ValueError(f"yin: no lag between fmax {fmax} and fmin {fmin} at sr {sr} (tau {tau_min} .. {tau_max})")
+    return lens, [1 + n // hop for n in lens], tau_min, tau_max
+
+
+def _yin_one(x, sr, hop, frame, tau_min, tau_max, threshold):
+    """One utterance: (f0 [T], cmnd [T, tau_max + 1]) in x's dtype."""
+    W = frame // 2
+    pad = torch.nn.functional.pad(x.view(1, 1, -1), (W, W), mode="reflect").view(-1)
+    fr = pad.unfold(0, frame, hop)  # [T, frame], T = 1 + N // hop
+    fr = fr - fr.mean(1, keepdim=True)
+    head = fr[:, :W]
+    T = fr.shape[0]
+    d = torch.empty(T, tau_max, dtype=x.dtype, device=x.device)  # column tau - 1
+    shifted = fr.unfold(1, W, 1)  # [T, W + 1, W] view: row tau = fr[:, tau : tau + W]
+    step = max(1, (1 << 24) // max(1, T * W))  # lags per batch of elementwise ops
+    for a in range(1, tau_max + 1, step):
+        b = min(tau_max + 1, a + step)
+        df = head.unsqueeze(1) - shifted[:, a:b]
+        d[:, a - 1:b - 1] = (df * df).sum(-1)
+    taus = torch.arange(1, tau_max + 1, dtype=x.dtype, device=x.device)
+    run = torch.cumsum(d, 1)
+    live = run > 0
+    cm = torch.where(live, d * taus / torch.where(live, run, torch.ones_like(run)), torch.ones_like(d))
+    cm = torch.cat([torch.ones(T, 1, dtype=x.dtype, device=x.device), cm], 1)  # [T, tau_max + 1], cmnd(0) = 1
+    idx = torch.arange(tau_max, device=x.device).unsqueeze(0)  # lags 0 .. tau_max - 1
+    below = (cm[:, :tau_max] < threshold) & (idx >= tau_min)
+    has = below.any(1)
+    first = torch.argmax(below.to(torch.uint8), 1, keepdim=True)
+    # walk down: the first lag t >= first at which t + 1 == tau_max or cmnd(t + 1) >= cmnd(t)
+    stop = ~(cm[:, 1:] < cm[:, :-1])
+    stop[:, -1] = True
+    t = torch.argmax((stop & (idx >= first)).to(torch.uint8), 1, keepdim=True)
+    t = torch.where(has.unsqueeze(1), t, torch.full_like(t, tau_min))  # any valid lag: the frame is zeroed below
+    # tau_min >= 2 and t < tau_max <= W: cmnd(t - 1) and cmnd(t + 1) always exist, so every lag is interpolated
+    a, b, c = cm.gather(1, t - 1), cm.gather(1, t), cm.gather(1, t + 1)
+    den = a - 2 * b + c
+    ok = den.abs() > 1e-12
+    lag = t.to(x.dtype) + torch.where(ok, 0.5 * (a - c) / torch.where(ok, den, torch.ones_like(den)),
+                                      torch.zeros_like(den))
+    f0 = (float(sr) / lag).squeeze(1)
+    voiced = has & (torch.sqrt((head * head).sum(1) / W) > 1e-4)
+    return torch.where(voiced, f0, torch.zeros_like(f0)), cm
+
+
+def yin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, threshold=0.15, return_cmnd=False):
+    """YIN fundamental frequency of packed utterances: ``wav`` one vector of all samples back to back, ``lengths``
+    the host sample counts.  Semantics of ``data.preprocess.yin_f0`` (centre reflect padding by frame / 2, 1 + N //
+    hop frames, frame mean removed, W = frame / 2) with the difference function accumulated from the squared
+    differences, d(tau) = sum_{j<W} (x[j] - x[j + tau])^2 (no cancellation: fp32 is enough), and cmnd(tau) = 1 where
+    the running sum of d is 0 (a frame that begins in digital silence has no pitch; ``yin_f0`` answers with rounding
+    noise there).  Lag: the first tau in [tau_min, tau_max) with cmnd < threshold, walked on while cmnd falls,
+    parabolic interpolation; a frame without a crossing or with rms(x[:W]) <= 1e-4 is unvoiced (0).
+    Computes in wav's dtype (float64 = the oracle) on wav's device.
+    -> f0 [R] over the packed frame rows (R = sum of 1 + N_b // hop), the per-utterance frame counts (host list) and,
+    with ``return_cmnd``, the plane [R, tau_max + 1]."""
+    lens, frames, tau_min, tau_max = yin_plan(wav, lengths, sr, hop, frame, fmin, fmax)
+    f0s, cms, at = [], [], 0
+    for n in lens:
+        f0, cm = _yin_one(wav[at:at + n], sr, int(hop), int(frame), tau_min, tau_max, threshold)
+        at += n
+        f0s.append(f0)
+        cms.append(cm)
+    f0 = torch.cat(f0s) if f0s else wav.new_zeros(0)
+    if return_cmnd:
+        return f0, frames, (torch.cat(cms) if cms else wav.new_zeros(0, tau_max + 1))
+    return f0, frames

@@ -3,7 +3,7 @@
 
 Reports achieved TFLOP/s (GEMM-shaped) or GB/s (memory-bound) per kernel, and
 the hipBLASLt number for the plain-GEMM equivalent (torch.matmul) as a yardstick.
-Usage (GPU box): python tools/bench_kernels.py [--rows 160000] [--iters 20] | --griffin-lim | --dtw | --align
+Usage (GPU box): python tools/bench_kernels.py [--rows 160000] [--iters 20] | --griffin-lim | --dtw | --align | --yin
 """
 import argparse
 import json
@@ -301,6 +301,127 @@ def bench_align(out_path, rounds=3):
             f.write(text)
 
 
+def yin_workloads(sr=22050, hop=256):
+    """(name, packed wav on the CPU, sample counts): 64 utterances with the LJSpeech ``val.txt`` frame-count
+    distribution (as ``dtw_workloads``) and one utterance of 800 frames.  The signal is six harmonics of an F0 that
+    wanders over 90 .. 250 Hz under a 3 Hz envelope, with noise-only stretches and 1 % noise: voiced, unvoiced and
+    quiet frames, as speech has them."""
+    import numpy as np
+
+    from speakingstyle_amd.data import synthetic
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    counts = synthetic.ljspeech_phone_counts(os.path.join(root, "preprocessed_data", "LJSpeech", "val.txt"))
+    rng = np.random.default_rng(0)
+    frames = np.clip(np.round(rng.choice(counts, size=64) * 8.1), 16, 1000).astype(np.int64)
+    out = []
+    for name, fr in (("64 utterances, LJSpeech val lengths", frames.tolist()), ("1 utterance, 800 frames", [800])):
+        wavs = []
+        for T in fr:
+            n = hop * (T - 1)
+            t = np.arange(n) / sr
+            f0 = 170 + 80 * np.sin(2 * np.pi * 1.1 * t + rng.uniform(0, 6.28))
+            ph = 2 * np.pi * np.cumsum(f0) / sr
+            s = sum(0.6 ** k * np.sin((k + 1) * ph + rng.uniform(0, 6.28)) for k in range(6))
+            voiced = np.sin(2 * np.pi * 0.8 * t + rng.uniform(0, 6.28)) > -0.4
+            x = np.where(voiced, 0.3 * (0.55 + 0.45 * np.sin(2 * np.pi * 3 * t)) * s, 0.0) + 0.01 * rng.standard_normal(n)
+            wavs.append(0.5 * x / np.abs(x).max())
+        out.append((name, torch.from_numpy(np.concatenate(wavs)).float(), [len(w) for w in wavs]))
+    return out
+
+
+def bench_yin(out_path, rounds=5, sr=22050, hop=256):
+    """``ops.yin`` (csrc/k_pitch.hip: one launch) against the torch reference ``ops.reference.yin`` on the same GPU
+    tensors and against numpy ``data.preprocess.yin_f0`` on the host.  The arms alternate in one process; every call is
+    timed wall-clock between two device synchronisations; the kernel alone is also timed with device events.  The
+    deviations of the kernel and of the float32 torch reference from the float64 torch reference on the same
+    workloads go to ``yin_numerics.txt`` beside the table."""
+    import time
+
+    import numpy as np
+
+    from speakingstyle_amd import ops
+    from speakingstyle_amd.data.preprocess import yin_f0
+    from speakingstyle_amd.ops import reference as ref
+
+    dev = torch.device("cuda")
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    lines = [f"Batched YIN, sr {sr} / hop {hop} / frame 1024 (lags 1 .. 311), fp32, {torch.cuda.get_device_name(0)}",
+             f"{rounds} alternating rounds per arm after 1 warm-up round; wall time per call between device syncs (ms);",
+             "kernel row: device-event time of one launch (3 warm-up launches before each), 20 samples", "",
+             f"{'workload':38s} {'arm':>28s} {'median':>10s} {'min':>10s} {'max':>10s}"]
+    num = [f"YIN kernel (csrc/k_pitch.hip) against the float64 torch reference, {torch.cuda.get_device_name(0)}; the "
+           "workloads of profiles/yin.txt", "",
+           "ref32 = the float32 torch reference on the same GPU, hip = the kernel; cmnd: maximum absolute deviation of the",
+           "plane from float64; disagree: frames whose voicing differs from float64 or whose F0 differs by more than 1e-3",
+           "relative; f0: maximum relative F0 error over the other voiced frames", "",
+           f"{'workload':38s} {'frames':>7s} {'voiced':>7s} {'max cmnd':>10s} {'cmnd ref32':>11s} {'cmnd hip':>10s} "
+           f"{'dis ref32':>9s} {'dis hip':>8s} {'f0 ref32':>10s} {'f0 hip':>10s}"]
+    for name, wav_h, lens in yin_workloads(sr, hop):
+        wav = wav_h.to(dev)
+        host = np.split(wav_h.numpy(), np.cumsum(lens)[:-1])
+        arms = (("hip ops.yin", lambda: ops.yin(wav, lens, sr, hop)),
+                ("torch reference, same GPU", lambda: ref.yin(wav, lens, sr, hop)),
+                ("numpy yin_f0, host", lambda: [yin_f0(w, sr, hop) for w in host]))
+        t = {a: [] for a, _ in arms}
+        for r in range(rounds + 1):
+            for arm, fn in arms:
+                ms = wall(fn)
+                if r >= 1:
+                    t[arm].append(ms)
+        for arm, v in t.items():
+            v.sort()
+            lines.append(f"{name:38s} {arm:>28s} {v[len(v) // 2]:10.3f} {v[0]:10.3f} {v[-1]:10.3f}")
+        a = t["hip ops.yin"]
+        for arm in ("torch reference, same GPU", "numpy yin_f0, host"):
+            b = t[arm]
+            lines.append(f"{'':38s} {arm + ' / hip':>28s} {b[len(b) // 2] / a[len(a) // 2]:10.1f}")
+        _, frames, tau_min, tau_max = ref.yin_plan(wav, lens, sr, hop)
+        pack = hip.YinPack(lens, frames, dev)
+        f0 = torch.empty(pack.R, device=dev)
+
+        def launch():
+            hip._check(hip.lib().ssamd_yin(hip._ptr(wav), hip._ptr(pack.off), hip._ptr(pack.n), hip._ptr(pack.rows), pack.R,
+                                           hop, 1024, tau_min, tau_max, float(sr), 0.15, hip._ptr(f0), None, hip._stream()),
+                       "ssamd_yin")
+
+        v = sorted(timeit(launch, 1) for _ in range(20))
+        lines.append(f"{name:38s} {'yin_kernel':>28s} {v[len(v) // 2]:10.3f} {v[0]:10.3f} {v[-1]:10.3f}")
+        flop = 3.0 * pack.R * tau_max * 512
+        lines.append(f"{'':38s} frames: {pack.R}, samples: {sum(lens)}, {flop / 1e9:.2f} GFLOP in the difference "
+                     f"function -> {flop / (v[len(v) // 2] * 1e-3) / 1e12:.2f} TFLOP/s at the median")
+        f64, _, c64 = ref.yin(wav.double(), lens, sr, hop, return_cmnd=True)
+        row = [f"{name:38s} {pack.R:7d} {int((f64 > 0).sum()):7d} {float(c64.max()):10.3e}"]
+        got = {"ref32": ref.yin(wav, lens, sr, hop, return_cmnd=True), "hip": ops.yin(wav, lens, sr, hop, return_cmnd=True)}
+        dev_c, dis, err = {}, {}, {}
+        for k, (f, _, c) in got.items():
+            f = f.double()
+            dev_c[k] = float((c.double() - c64).abs().max())
+            both = (f > 0) & (f64 > 0)
+            rel = (f - f64).abs() / f64.clamp(min=1.0)
+            bad = ((f > 0) != (f64 > 0)) | (both & (rel > 1e-3))
+            dis[k] = int(bad.sum())
+            err[k] = float(rel[both & ~bad].max()) if (both & ~bad).any() else 0.0
+        row.append(f"{dev_c['ref32']:11.3e} {dev_c['hip']:10.3e} {dis['ref32']:9d} {dis['hip']:8d} {err['ref32']:10.3e} "
+                   f"{err['hip']:10.3e}")
+        num.append(" ".join(row))
+    for text, path in (("\n".join(lines) + "\n", out_path),
+                       ("\n".join(num) + "\n", out_path and os.path.join(os.path.dirname(os.path.abspath(out_path)),
+                                                                         "yin_numerics.txt"))):
+        print(text, end="", flush=True)
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=160000)
@@ -312,10 +433,15 @@ def main():
                     help="only the DTW arm: HIP kernels vs the torch wavefront, table written to --out")
     ap.add_argument("--align", action="store_true",
                     help="only the alignment arm: forward-sum / MAS kernels vs the torch loop and F.ctc_loss")
+    ap.add_argument("--yin", action="store_true",
+                    help="only the pitch arm: the YIN kernel vs the torch reference on the GPU and numpy on the host "
+                         "(yin_numerics.txt is written beside --out)")
     ap.add_argument("--out", default=None,
-                    help="default: profiles/griffin_lim.txt, profiles/dtw.txt, profiles/align.txt")
+                    help="default: profiles/griffin_lim.txt, profiles/dtw.txt, profiles/align.txt, profiles/yin.txt")
     args = ap.parse_args()
     prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    if args.yin:
+        return bench_yin(args.out or os.path.join(prof, "yin.txt"))
     if args.align:
         return bench_align(args.out or os.path.join(prof, "align.txt"))
     if args.dtw:
