@@ -9,7 +9,8 @@
   objective metrics of free-running synthesis against the recordings (MCD, F0 / energy error along a DTW path):
     python analyze.py objective --restore_step 900000 -p P -m M -t T [--source val.txt] [--out_dir analysis]
         [--pitch_control 1 --energy_control 1 --duration_control 1] [--n_ceps 13] [--batch_size 32] [--cpu]
-        [--wave [--vocoder griffin_lim]]   (pitch and MCD of the vocoded audio against the recordings)
+        [--wave [--vocoder griffin_lim] [--pitch_tracker pyin]]   (pitch and MCD of the vocoded audio against the
+                                                                   recordings)
 """
 import argparse
 import json
@@ -19,7 +20,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("command", choices=["variance", "inspect", "objective"])
     ap.add_argument("--restore_step", type=int, default=0)
@@ -41,9 +42,16 @@ def main(argv=None):
                          "wave_f0_rmse_cents")
     ap.add_argument("--vocoder", choices=["griffin_lim", "hifigan"], default=None,
                     help="objective --wave: the vocoder (default: the model config's; griffin_lim needs no checkpoint)")
+    ap.add_argument("--pitch_tracker", choices=["yin", "pyin"], default="yin",
+                    help="objective --wave: the F0 tracker of both waveforms (pyin: probabilistic YIN, one smooth "
+                         "track per utterance; keeps the voiced frames of noisy vocoded audio that yin drops)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--cpu", action="store_true")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
 
     import torch
 
@@ -65,7 +73,8 @@ def main(argv=None):
 
         src = a.source or os.path.join(configs[0]["path"]["preprocessed_path"], "val.txt")
         rep = evaluate_objective(model, configs, src, dev, (a.pitch_control, a.energy_control, a.duration_control),
-                                 a.batch_size or 32, a.out_dir, a.n_ceps, wave=a.wave, vocoder=a.vocoder)
+                                 a.batch_size or 32, a.out_dir, a.n_ceps, wave=a.wave, vocoder=a.vocoder,
+                                 pitch_tracker=a.pitch_tracker)
     else:
         from speakingstyle_amd.analysis.inspect import inspect_batch
 

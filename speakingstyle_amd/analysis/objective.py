@@ -19,7 +19,9 @@ alignment: its path metrics are nan, it is counted in ``n_empty`` and left out o
 Waveform-level figures (``wave_metrics``, ``evaluate_objective(wave=True)``): the figures above compare what the model
 predicts; these compare what is heard.  Both waveforms -- the vocoded synthesis and the recording -- go through the
 same front end (log-mel -> cepstra -> ``ops.dtw``) and the same pitch tracker (``ops.yin``: one HIP workgroup per
-frame on the GPU), and the F0 tracks are gathered along the path (Skerry-Ryan et al. 2018, after Chu & Alwan 2009):
+frame on the GPU; or ``ops.pyin``, probabilistic YIN, which decodes one smooth track per utterance and keeps the
+voiced frames of noisy vocoded audio that a fixed threshold drops), and the F0 tracks are gathered along the path
+(Skerry-Ryan et al. 2018, after Chu & Alwan 2009):
 
   wave_mcd_db         ``mcd_db`` of the audio
   wave_vde            voicing decision error: share of path cells voiced on one side only
@@ -46,6 +48,7 @@ MCD_SCALE = 10.0 * math.sqrt(2.0) / math.log(10.0)
 METRICS = ("mcd_db", "logmel_l1", "pitch_rmse", "energy_rmse", "pitch_corr", "dur_mae_frames", "len_ratio")
 WAVE_METRICS = ("wave_mcd_db", "wave_vde", "wave_gpe", "wave_ffe", "wave_f0_rmse_cents")
 GROSS_PITCH_ERROR = 0.2  # relative F0 deviation from the y side that counts as gross
+PITCH_TRACKERS = ("yin", "pyin")
 
 
 def dct_matrix(n_mel: int, n_ceps: int, device=None, dtype=torch.float32) -> torch.Tensor:
@@ -181,18 +184,23 @@ def _logmel_rows(wav, lens, stft):
 
 
 @torch.no_grad()
-def wave_metrics(wav_a, lens_a, wav_b, lens_b, pp, n_ceps: int = 13, frame: int = 1024) -> Dict[str, np.ndarray]:
+def wave_metrics(wav_a, lens_a, wav_b, lens_b, pp, n_ceps: int = 13, frame: int = 1024,
+                 tracker: str = "yin") -> Dict[str, np.ndarray]:
     """Waveform-level metrics of P pairs of utterances: ``wav_a`` / ``wav_b`` packed fp32 samples in [-1, 1] on one
     device (all utterances back to back) with host sample counts ``lens_a`` / ``lens_b``; ``pp`` the preprocess
     config (sampling rate, STFT, mel).  Log-mel of both sides -> cepstra -> ``ops.dtw``; ``ops.yin`` (``frame``
-    samples per analysis frame) on both sides; F0 gathered along the path.  a is the x side of the alignment, b the
-    y side and the pitch reference.  -> {metric of ``WAVE_METRICS``: float64 [P]} plus ``path_len``."""
+    samples per analysis frame; ``tracker="pyin"``: ``ops.pyin``) on both sides; F0 gathered along the path.  a is the
+    x side of the alignment, b the y side and the pitch reference.  -> {metric of ``WAVE_METRICS``: float64 [P]} plus
+    ``path_len``."""
+    if tracker not in PITCH_TRACKERS:
+        raise ValueError(f"pitch tracker {tracker!r} not supported ({', '.join(PITCH_TRACKERS)})")
+    track = ops.yin if tracker == "yin" else ops.pyin
     lens_a, lens_b = [int(v) for v in lens_a], [int(v) for v in lens_b]
     pre = pp["preprocessing"]
     sr, hop = pre["audio"]["sampling_rate"], pre["stft"]["hop_length"]
     wav_a, wav_b = wav_a.float().contiguous(), wav_b.float().contiguous()
-    fa, frames_a = ops.yin(wav_a, lens_a, sr, hop, frame)  # also checks the lengths before anything else runs
-    fb, frames_b = ops.yin(wav_b, lens_b, sr, hop, frame)
+    fa, frames_a = track(wav_a, lens_a, sr, hop, frame)[:2]  # also checks the lengths before anything else runs
+    fb, frames_b = track(wav_b, lens_b, sr, hop, frame)[:2]
     stft = _front_end(pp)
     mel_a, mel_b = _logmel_rows(wav_a, lens_a, stft), _logmel_rows(wav_b, lens_b, stft)
     cost, path, plen = align(mel_a, frames_a, mel_b, frames_b, n_ceps)
@@ -270,7 +278,8 @@ def _summary(rows: List[dict], metrics=METRICS) -> Dict:
 
 @torch.no_grad()
 def evaluate_objective(model, configs, source: str, device, controls=(1.0, 1.0, 1.0), batch_size: int = 32,
-                       out_dir: Optional[str] = None, n_ceps: int = 13, wave: bool = False, vocoder=None) -> Dict:
+                       out_dir: Optional[str] = None, n_ceps: int = 13, wave: bool = False, vocoder=None,
+                       pitch_tracker: str = "yin") -> Dict:
     """Free-running synthesis (no targets, predicted durations) of every utterance of ``source`` (a ``val.txt``-style
     list) against its stored mel / pitch / energy / duration; one ``ops.dtw`` call per batch of pairs.
     -> {"n", "n_empty", "mean": {metric: value}, "median": {...}}; with ``out_dir`` also ``objective_summary.json``
@@ -278,8 +287,9 @@ def evaluate_objective(model, configs, source: str, device, controls=(1.0, 1.0, 
 
     ``wave``: also the waveform-level ``WAVE_METRICS`` -- every synthesized mel is vocoded (``vocoder``: None = the
     configured one, ``"griffin_lim"`` needs no checkpoint, ``"hifigan"``, or a vocoder object) and compared with the
-    recording ``<raw_path>/<speaker>/<basename>.wav`` at the configured rate (``wave_metrics``).  A synthesis too
-    short for the pitch tracker's frame has nan there."""
+    recording ``<raw_path>/<speaker>/<basename>.wav`` at the configured rate (``wave_metrics``, F0 of both sides by
+    ``pitch_tracker``; the summary names a tracker other than ``yin`` as ``"pitch_tracker"``).  A synthesis too short
+    for the pitch tracker's frame has nan there."""
     from torch.utils.data import DataLoader
 
     from ..data.dataset import TextDataset, to_device
@@ -294,6 +304,8 @@ def evaluate_objective(model, configs, source: str, device, controls=(1.0, 1.0, 
     speaker_of = dict(zip(ds.basename, ds.speaker))
     dev = torch.device(device)
     model.eval()
+    if pitch_tracker not in PITCH_TRACKERS:
+        raise ValueError(f"pitch tracker {pitch_tracker!r} not supported ({', '.join(PITCH_TRACKERS)})")
     if wave:
         from ..audio.io import read_wav
 
@@ -352,7 +364,7 @@ def evaluate_objective(model, configs, source: str, device, controls=(1.0, 1.0, 
             if wkeep:
                 wres = wave_metrics(torch.cat([syn[i] for i in wkeep]), [syn[i].shape[0] for i in wkeep],
                                     torch.cat([rec[i] for i in wkeep]), [rec[i].shape[0] for i in wkeep], pp, n_ceps,
-                                    yin_frame)
+                                    yin_frame, pitch_tracker)
         at = {i: k for k, i in enumerate(keep)}
         for i, base in enumerate(names):
             row = {"basename": base, "pred_frames": int(mel_lens[i]), "true_frames": int(truth[i][0].shape[0])}
@@ -366,6 +378,8 @@ def evaluate_objective(model, configs, source: str, device, controls=(1.0, 1.0, 
                 row[m] = float(wres[m][wat[i]]) if i in wat else float("nan")
             rows.append(row)
     summary = _summary(rows, METRICS + WAVE_METRICS if wave else METRICS)
+    if wave and pitch_tracker != "yin":
+        summary["pitch_tracker"] = pitch_tracker
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "objective_summary.json"), "w") as f:

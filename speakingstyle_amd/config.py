@@ -171,7 +171,7 @@ def normalize_preprocess_config(cfg: Config | None) -> Config:
     out = _merge(_PREPROCESS_DEFAULTS, cfg)
     pp = out["preprocessing"]
     _check_enum(pp["pitch"]["feature"], ["phoneme_level", "frame_level"], "preprocessing.pitch.feature")
-    _check_enum(pp["pitch"].get("extractor", "dio"), ["dio", "yin"], "preprocessing.pitch.extractor")
+    _check_enum(pp["pitch"].get("extractor", "dio"), ["dio", "yin", "pyin"], "preprocessing.pitch.extractor")
     _check_enum(pp["energy"]["feature"], ["phoneme_level", "frame_level"], "preprocessing.energy.feature")
     _check_enum(pp["duration"]["source"], ["textgrid", "learned"], "preprocessing.duration.source")
     return out

@@ -13,7 +13,8 @@ pyworld's algorithm pair DIO + StoneMask re-implemented in the native host
 runtime (``csrc/host_f0.cpp``, ``utils/native.dio/stonemask``), same frame period
 (hop / sr) and 0 = unvoiced convention; numerical parity with pyworld itself is
 unpinned (the library is not installable here).  ``preprocessing.pitch.extractor:
-yin`` selects the vectorised YIN tracker below instead.
+yin`` selects the vectorised YIN tracker below instead, ``pyin`` probabilistic YIN (``ops.pyin`` on a host tensor:
+one smooth track per utterance, F0 quantised to bins of 2.5 cents).
 Utterances are processed by a multiprocessing pool (the reference uses
 joblib+dask, ``preprocessor/bc_2013.py:62-73``).
 
@@ -152,7 +153,15 @@ def extract_f0(wav: np.ndarray, sr: int, hop: int, method: str = "dio") -> np.nd
         return native.stonemask(x, f0, t, sr)
     if method == "yin":
         return yin_f0(wav, sr, hop)
-    raise ValueError(f"unknown pitch extractor {method!r} (dio | yin)")
+    if method == "pyin":
+        import torch
+
+        from .. import ops
+
+        # a host tensor: the workers of the preprocessing pool never open the GPU
+        x = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+        return ops.pyin(x, [x.shape[0]], sr, hop)[0].double().numpy()
+    raise ValueError(f"unknown pitch extractor {method!r} (dio | yin | pyin)")
 
 
 def interpolate_unvoiced(pitch: np.ndarray) -> np.ndarray:

@@ -429,6 +429,32 @@ def yin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, threshold=0.15
     return fn(wav, lengths, sr, hop, frame, fmin, fmax, threshold, return_cmnd)
 
 
+def pyin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, bins_per_semitone=20, max_transition_rate=35.92,
+         switch_prob=0.01, no_trough_prob=0.01, return_obs=False):
+    """Probabilistic YIN of packed utterances (layout and frame counts of ``yin``) -> (f0 [R], the bin centre of the
+    decoded track, 0 = unvoiced; the frame counts as a host list; voiced_prob [R][; the candidate plane obs [R, NB]]);
+    see ``ops.reference.pyin``.  On the GPU the YIN kernel's cmnd plane, a wave per frame row for the candidates and
+    a workgroup per utterance for the Viterbi decode (``csrc/k_pyin.hip``)."""
+    fn = _hip().pyin if use_hip(wav) else ref.pyin
+    return fn(wav, lengths, sr, hop, frame, fmin, fmax, bins_per_semitone, max_transition_rate, switch_prob,
+              no_trough_prob, return_obs)
+
+
+def pyin_obs(cm, sr, tau_min, tau_max, fmin=71.0, fmax=800.0, bins_per_semitone=20, no_trough_prob=0.01):
+    """Stage 1 of ``pyin``: the cmnd plane [R, tau_max + 1] -> (obs [R, NB], voiced_prob [R]); see
+    ``ops.reference.pyin_obs``."""
+    fn = _hip().pyin_obs if use_hip(cm) else ref.pyin_obs
+    return fn(cm, sr, tau_min, tau_max, fmin, fmax, bins_per_semitone, no_trough_prob)
+
+
+def pyin_decode(obs, voiced_prob, frames, sr, hop, fmin=71.0, bins_per_semitone=20, max_transition_rate=35.92,
+                switch_prob=0.01):
+    """Stage 2 of ``pyin``: the Viterbi track of every utterance of the packed planes (host frame counts ``frames``)
+    -> f0 [R]; see ``ops.reference.pyin_decode``."""
+    fn = _hip().pyin_decode if use_hip(obs) else ref.pyin_decode
+    return fn(obs, voiced_prob, frames, sr, hop, fmin, bins_per_semitone, max_transition_rate, switch_prob)
+
+
 def align_forward_sum(lp, t_lens, n_lens):
     """Forward-sum alignment loss (CTC without blanks) over the monotone alignments of a padded batch:
     lp [B, Tmax, Nmax] fp32, ``t_lens`` / ``n_lens`` the frames / tokens per utterance (host sequences or tensors)

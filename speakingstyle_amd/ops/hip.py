@@ -3048,6 +3048,126 @@ def yin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, threshold=0.15
     return (f0, frames, cm) if return_cmnd else (f0, frames)
 
 
+# ------------------------------------------------------------------------ probabilistic YIN (csrc/k_pyin.hip)
+_SIGS.update({"ssamd_pyin_obs": [P, I, I, I, F, F, F, I, F, P, P, P],
+              "ssamd_pyin_viterbi": [P, P, P, I, I, I, I, P, F, F, F, F, P, P, P]})
+
+# Back-pointer budget of one pyin_viterbi launch, in bytes of the stream's workspace: an utterance of T frames takes
+# T * 2 * NB bytes (1.3 MiB at 800 frames), so 256 MiB hold ~190 of them; a larger batch runs in several launches over
+# the same workspace.  A chunk always holds at least one utterance.
+PYIN_PLANE_BUDGET = 256 << 20
+# Bins per thread of pyin_viterbi_kernel (2: 512 threads, two waves per SIMD; 4: 256 threads, one).  Measured on an
+# MI355X, 800 frames: 6.5 ms against 7.5 ms (profiles/pyin.txt).  Of the 6.5 ms, 0.15 ms are the back-trace, 0.77 ms
+# the per-frame work outside the band (a band of one cell takes that long) and the rest the band's compare-and-select
+# instructions, ~0.14 us per step of 2 x 4 candidates; reading the next step's cells ahead changed nothing (6.6 ms).
+PYIN_BINS_PER_THREAD = 2
+
+
+def pyin_obs(cm, sr, tau_min, tau_max, fmin=71.0, fmax=800.0, bins_per_semitone=20, no_trough_prob=0.01):
+    """``ops.reference.pyin_obs`` on the GPU (fp32): one ``pyin_obs_kernel`` launch, a wave per row of the cmnd plane
+    -> obs [R, NB], voiced_prob [R]."""
+    _need(cm, torch.float32, "pyin_obs.cm")
+    tau_min, tau_max, bps = int(tau_min), int(tau_max), int(bins_per_semitone)
+    if cm.dim() != 2 or cm.shape[1] != tau_max + 1 or not 2 <= tau_min < tau_max <= 1024:
+        raise ValueError(f"pyin_obs: cmnd plane {tuple(cm.shape)} is not [R, tau_max + 1] for lags {tau_min} .. {tau_max} "
+                         "(2 <= tau_min < tau_max <= 1024)")
+    NB = int(math.floor(12 * bps * math.log2(fmax / fmin))) + 1
+    if not 1 <= NB <= ref.PYIN_MAX_BINS:
+        raise ValueError(f"pyin_obs: NB = {NB} bins outside the kernel's 1 .. {ref.PYIN_MAX_BINS}")
+    R, dev = cm.shape[0], cm.device
+    if R * max(NB, tau_max + 1) >= 2 ** 31:
+        raise ValueError("pyin_obs: packed row counts are 32-bit")
+    obs = torch.empty(R, NB, device=dev, dtype=torch.float32)
+    vp = torch.empty(R, device=dev, dtype=torch.float32)
+    rc = lib().ssamd_pyin_obs(_ptr(cm), R, tau_min, tau_max, float(sr), float(fmin), float(12 * bps), NB,
+                              float(no_trough_prob), _ptr(obs), _ptr(vp), _stream())
+    _check(rc, "ssamd_pyin_obs")
+    return obs, vp
+
+
+class PyinPlan:
+    """Device tables of a packed pYIN decode, built from the host frame counts and uploaded in one copy: ``meta`` int32
+    [n, 4] = {first packed row, frames, plane byte offset (two halves, each chunk's counted from 0)}, ``tab`` the
+    log-triangle weights of the band padded with -inf to the kernel's steps, and ``chunks`` = (first utterance, end
+    utterance, plane bytes) of consecutive utterances whose back-pointer planes fit the budget."""
+
+    def __init__(self, frames, NB, h, device, plane_budget=None, bins_per_thread=None):
+        import numpy as np
+
+        budget = PYIN_PLANE_BUDGET if plane_budget is None else int(plane_budget)
+        n = self.n = len(frames)
+        stride = (NB + 3) // 4 * 4
+        meta, row, p0, used = np.zeros((n, 2), dtype=np.int64), 0, 0, 0
+        self.chunks = []
+        for u, T in enumerate(frames):
+            size = T * 2 * stride
+            if u > p0 and used + size > budget:
+                self.chunks.append((p0, u, used))
+                p0, used = u, 0
+            meta[u] = (row | (T << 32), used)  # little-endian: {row, T} and the offset's two halves as int32
+            row += T
+            used += size
+        if n:
+            self.chunks.append((p0, n, used))
+        B = self.bins_per_thread = PYIN_BINS_PER_THREAD if bins_per_thread is None else int(bins_per_thread)
+        hA = (h + B - 1) // B * B
+        steps = (2 * hA + B) // B
+        d = torch.arange(-h, h + 1, dtype=torch.float32)
+        tab = torch.full((B * (steps + 1),), float("-inf"), dtype=torch.float32)
+        at = B - 1 + hA - h
+        tab[at:at + 2 * h + 1] = torch.log((h + 1 - d.abs()) / float((h + 1) ** 2))  # as the float32 reference takes it
+        host = torch.from_numpy(np.concatenate([meta.reshape(-1).view(np.int32), tab.numpy().view(np.int32)]))
+        self.buf = (host.pin_memory() if device.type == "cuda" else host).to(device, non_blocking=True)
+        self.meta, self.tab = self.buf[:4 * n], self.buf[4 * n:]
+        self.ws_floats = (max([c[2] for c in self.chunks] + [0]) + 3) // 4
+
+
+def pyin_decode(obs, voiced_prob, frames, sr, hop, fmin=71.0, bins_per_semitone=20, max_transition_rate=35.92,
+                switch_prob=0.01, plane_budget=None, bins_per_thread=None):
+    """``ops.reference.pyin_decode`` on the GPU (fp32): one ``pyin_viterbi_kernel`` launch (a workgroup per utterance:
+    forward pass and back-trace; back-pointer planes in the stream's workspace) per chunk of utterances whose planes
+    fit ``plane_budget`` bytes (default ``PYIN_PLANE_BUDGET``).  ``frames`` is a host sequence: nothing here waits for
+    the device.  Every utterance comes out bitwise as if alone.  -> f0 [R] fp32."""
+    _need(obs, torch.float32, "pyin_decode.obs")
+    _need(voiced_prob, torch.float32, "pyin_decode.voiced_prob")
+    frames = [int(v) for v in frames]
+    if obs.dim() != 2 or voiced_prob.shape != obs.shape[:1] or sum(frames) != obs.shape[0] or min(frames + [0]) < 0:
+        raise ValueError(f"pyin_decode: obs {tuple(obs.shape)} / voiced_prob {tuple(voiced_prob.shape)} do not hold the "
+                         f"{sum(frames)} frames of the utterances")
+    bps, NB = int(bins_per_semitone), obs.shape[1]
+    h = max(1, int(round(max_transition_rate * 12 * int(hop) / sr))) * bps // 2
+    if h > ref.PYIN_MAX_HALF or not 1 <= NB <= ref.PYIN_MAX_BINS:
+        raise ValueError(f"pyin_decode: h = {h} / NB = {NB} outside the decoder's h <= {ref.PYIN_MAX_HALF}, NB <= "
+                         f"{ref.PYIN_MAX_BINS}")
+    R, dev = obs.shape[0], obs.device
+    if R * NB >= 2 ** 31:
+        raise ValueError("pyin_decode: packed row counts are 32-bit")
+    f0 = torch.empty(R, device=dev, dtype=torch.float32)
+    if R == 0:
+        return f0
+    plan = PyinPlan(frames, NB, h, dev, plane_budget, bins_per_thread)
+    ws = _workspace(dev, plan.ws_floats)
+    for a, b, _ in plan.chunks:  # the launches of a stream run in order: the next chunk reuses the planes
+        rc = lib().ssamd_pyin_viterbi(_ptr(obs), _ptr(voiced_prob), _ptr(plan.meta[4 * a:]), b - a, NB, h, plan.bins_per_thread,
+                                      _ptr(plan.tab), math.log(1.0 - switch_prob), math.log(switch_prob), float(fmin), float(12 * bps),
+                                      _ptr(ws), _ptr(f0), _stream())
+        _check(rc, "ssamd_pyin_viterbi")
+    return f0
+
+
+def pyin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, bins_per_semitone=20, max_transition_rate=35.92,
+         switch_prob=0.01, no_trough_prob=0.01, return_obs=False):
+    """``ops.reference.pyin`` on the GPU (fp32): ``yin_kernel`` with its cmnd plane, ``pyin_obs_kernel`` and
+    ``pyin_viterbi_kernel`` on one stream.  ``lengths`` is a host sequence: nothing here waits for the device.
+    -> f0 [R] fp32, the per-utterance frame counts (host list), voiced_prob [R][, obs [R, NB]]."""
+    _, _, tau_min, tau_max, NB, h = ref.pyin_plan(wav, lengths, sr, hop, frame, fmin, fmax, bins_per_semitone,
+                                                  max_transition_rate)
+    _, frames, cm = yin(wav, lengths, sr, hop, frame, fmin, fmax, return_cmnd=True)
+    obs, vp = pyin_obs(cm, sr, tau_min, tau_max, fmin, fmax, bins_per_semitone, no_trough_prob)
+    f0 = pyin_decode(obs, vp, frames, sr, hop, fmin, bins_per_semitone, max_transition_rate, switch_prob)
+    return (f0, frames, vp, obs) if return_obs else (f0, frames, vp)
+
+
 # ------------------------------------------------------------------------ alignment learning (csrc/k_align.hip)
 _SIGS.update({"ssamd_align_fsum_fwd": [P, P, P, I, I, I, I, P, P, P],
               "ssamd_align_fsum_bwd": [P, P, P, P, P, P, I, I, I, I, P, P],

@@ -608,3 +608,172 @@ def yin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, threshold=0.15
     if return_cmnd:
         return f0, frames, (torch.cat(cms) if cms else wav.new_zeros(0, tau_max + 1))
     return f0, frames
+
+
+# --------------------------------------------------------- probabilistic YIN (csrc/k_pyin.hip semantics)
+PYIN_MAX_HALF = 63    # the kernel keeps a band offset 0 .. 2 h and a switch bit in one byte
+PYIN_MAX_BINS = 1024  # ... and four bins per lane of a 256-thread workgroup
+PYIN_LOG_FLOOR = 1e-30
+
+
+def pyin_bins(sr, hop, fmin=71.0, fmax=800.0, bins_per_semitone=20, max_transition_rate=35.92):
+    """Pitch grid of the pYIN decoder -> (NB bins of 1 / bins_per_semitone semitones from fmin up to fmax, band
+    half-width h in bins a track may move per frame).  ``ValueError`` with the value when h > 63 or NB > 1024."""
+    bps = int(bins_per_semitone)
+    if bps < 1 or not 0 < fmin < fmax:
+        raise ValueError(f"pyin: bins_per_semitone {bins_per_semitone} / fmin {fmin} / fmax {fmax} give no pitch grid")
+    NB = int(math.floor(12 * bps * math.log2(fmax / fmin))) + 1
+    st = max(1, int(round(max_transition_rate * 12 * int(hop) / sr)))
+    h = st * bps // 2
+    if NB > PYIN_MAX_BINS:
+        raise ValueError(f"pyin: {bps} bins per semitone between {fmin} and {fmax} Hz are NB = {NB} bins; the decoder "
+                         f"covers NB <= {PYIN_MAX_BINS}")
+    if h > PYIN_MAX_HALF:
+        raise ValueError(f"pyin: hop {hop} at sr {sr} lets a track move h = {h} bins per frame; the decoder covers "
+                         f"h <= {PYIN_MAX_HALF}")
+    return NB, h
+
+
+def pyin_plan(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, bins_per_semitone=20,
+              max_transition_rate=35.92):
+    """Host side of a packed pYIN batch, validated: ``yin_plan``'s (sample counts, frame counts, tau_min, tau_max)
+    followed by ``pyin_bins``' (NB, h)."""
+    plan = yin_plan(wav, lengths, sr, hop, frame, fmin, fmax)
+    return plan + pyin_bins(sr, hop, fmin, fmax, bins_per_semitone, max_transition_rate)
+
+
+def _beta_2_18_tail(x):
+    """1 - F(x) of Beta(2, 18), the prior of the YIN threshold: (1 - x)^18 (1 + 18 x), x clamped to [0, 1].  The
+    weights below are differences of F; taken between the tails they keep their relative precision where F is
+    within rounding of 1 (a trough at cmnd 0.8 weighs 4e-12: float32 holds that as a tail, not as 1 - F)."""
+    x = x.clamp(0.0, 1.0)
+    y = 1.0 - x
+    y2 = y * y
+    y4 = y2 * y2
+    y8 = y4 * y4
+    return (y8 * y8 * y2) * (1.0 + 18.0 * x)
+
+
+def pyin_obs(cm, sr, tau_min, tau_max, fmin=71.0, fmax=800.0, bins_per_semitone=20, no_trough_prob=0.01):
+    """Stage 1 of pYIN, every frame row alone: the cmnd plane ``cm`` [R, tau_max + 1] of ``yin`` -> (obs [R, NB]
+    probability of every pitch bin, voiced_prob [R]) in cm's dtype.
+
+    Troughs are the lags t in [tau_min, tau_max - 1] with cm[t] < cm[t - 1] and cm[t] <= cm[t + 1].  With the YIN
+    threshold distributed as Beta(2, 18) (CDF F), a trough below every earlier trough (m = the smallest cmnd of the
+    earlier ones, 2 at the start) is YIN's pick for the thresholds in (cm[t], m] and weighs F(m) - F(cm[t]); the
+    lowest trough (the first of equals) also takes no_trough_prob * F(cm[t]), the thresholds no trough is below.
+    Every weighted trough is interpolated as in ``yin`` and lands in bin round(12 bps log2(sr / lag / fmin)),
+    clamped to the grid; weights of one bin are added in increasing lag order; voiced_prob is their clamped sum."""
+    bps = int(bins_per_semitone)
+    NB = int(math.floor(12 * bps * math.log2(fmax / fmin))) + 1
+    R = cm.shape[0]
+    dt, dev = cm.dtype, cm.device
+    obs = torch.zeros(R, NB, dtype=dt, device=dev)
+    vp = torch.zeros(R, dtype=dt, device=dev)
+    if R == 0:
+        return obs, vp
+    a, b, c = cm[:, tau_min - 1:tau_max - 1], cm[:, tau_min:tau_max], cm[:, tau_min + 1:tau_max + 1]
+    trough = (b < a) & (b <= c)
+    two = torch.full_like(b, 2.0)
+    low = torch.cummin(torch.where(trough, b, two), 1).values
+    m = torch.cat([two[:, :1], low[:, :-1]], 1)  # the smallest cmnd of the earlier troughs
+    rec = trough & (b < m)
+    K = int(rec.sum(1).max())
+    if K == 0:
+        return obs, vp
+    Sb = _beta_2_18_tail(b)
+    w = Sb - _beta_2_18_tail(m)  # F(m) - F(cm[t])
+    lags = torch.arange(tau_min, tau_max, device=dev)
+    last = torch.where(rec, lags, torch.zeros_like(lags)).argmax(1, keepdim=True)  # the lowest trough
+    w = w.scatter_add(1, last, no_trough_prob * (1.0 - Sb.gather(1, last)))
+    den = a - 2 * b + c
+    ok = den.abs() > 1e-12
+    lag = lags.to(dt) + torch.where(ok, 0.5 * (a - c) / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den))
+    bins = torch.round(12 * bps * torch.log2(float(sr) / lag / float(fmin))).clamp(0, NB - 1)
+    bins = torch.where(rec, bins, torch.zeros_like(bins)).to(torch.long)  # elsewhere the parabola means nothing
+    # the record troughs of every row, compacted in lag order: one add per row and step keeps the order on any device
+    order = torch.where(rec, lags, torch.full_like(lags, tau_max)).sort(1).values[:, :K]
+    live = order < tau_max
+    col = (order - tau_min).clamp(max=tau_max - tau_min - 1)
+    wk = torch.where(live, w.gather(1, col), torch.zeros_like(vp).unsqueeze(1))
+    bk = bins.gather(1, col)
+    for k in range(K):
+        obs.scatter_add_(1, bk[:, k:k + 1], wk[:, k:k + 1])
+        vp = vp + wk[:, k]
+    return obs, vp.clamp(0.0, 1.0)
+
+
+def pyin_decode(obs, voiced_prob, frames, sr, hop, fmin=71.0, bins_per_semitone=20, max_transition_rate=35.92,
+                switch_prob=0.01):
+    """Stage 2 of pYIN, every utterance alone: Viterbi over 2 NB states (voiced bin b, unvoiced bin b) of the planes
+    of ``pyin_obs`` (packed rows, ``frames`` the host frame counts) -> f0 [R]: the centre fmin 2^(b / (12 bps)) of
+    the decoded bin on voiced frames, 0 on unvoiced ones.
+
+    Log observation log(max(obs, 1e-30)) for a voiced state, log(max((1 - voiced_prob) / NB, 1e-30)) for an unvoiced
+    one; uniform start; a bin moves by d in [-h, h] with weight (h + 1 - |d|) / (h + 1)^2 (moves off the grid do not
+    exist), keeping the voicing costs log(1 - switch_prob), switching log(switch_prob).  After every frame the
+    maximum over all states is subtracted.  Ties: the lowest predecessor bin, then staying over switching; at the
+    last frame voiced over unvoiced, then the lowest bin."""
+    bps = int(bins_per_semitone)
+    NB = obs.shape[1]
+    frames = [int(v) for v in frames]
+    if obs.dim() != 2 or voiced_prob.shape != obs.shape[:1] or sum(frames) != obs.shape[0]:
+        raise ValueError(f"pyin_decode: obs {tuple(obs.shape)} / voiced_prob {tuple(voiced_prob.shape)} do not hold the "
+                         f"{sum(frames)} frames of the utterances")
+    st = max(1, int(round(max_transition_rate * 12 * int(hop) / sr)))
+    h = st * bps // 2
+    if h > PYIN_MAX_HALF or not 1 <= NB <= PYIN_MAX_BINS:
+        raise ValueError(f"pyin_decode: h = {h} / NB = {NB} outside the decoder's h <= {PYIN_MAX_HALF}, NB <= "
+                         f"{PYIN_MAX_BINS}")
+    dt, dev = obs.dtype, obs.device
+    d = torch.arange(-h, h + 1, dtype=dt, device=dev)
+    ltri = torch.log((h + 1 - d.abs()) / float((h + 1) ** 2))
+    stay = torch.tensor(math.log(1.0 - switch_prob), dtype=dt, device=dev)
+    swap = torch.tensor(math.log(switch_prob), dtype=dt, device=dev)
+    centres = float(fmin) * torch.exp2(torch.arange(NB, dtype=dt, device=dev) / (12 * bps))
+    pad = torch.full((2, h), float("-inf"), dtype=dt, device=dev)
+    out, at = [], 0
+    for T in frames:
+        if T == 0:
+            continue
+        lo = torch.stack([torch.log(obs[at:at + T].clamp(min=PYIN_LOG_FLOOR)),
+                          torch.log(((1.0 - voiced_prob[at:at + T]) / NB).clamp(min=PYIN_LOG_FLOOR)).unsqueeze(1)
+                          .expand(T, NB)], 1)  # [T, 2, NB]
+        at += T
+        delta = lo[0] - lo[0].max()
+        back = torch.empty(T, 2, NB, dtype=torch.long, device=dev)  # predecessor: voicing * NB + bin
+        base = torch.arange(NB, device=dev) - h
+        for t in range(1, T):
+            win = torch.cat([pad, delta, pad], 1).unfold(1, 2 * h + 1, 1) + ltri  # [2, NB, 2 h + 1]
+            best, off = win.max(2)  # the first of equal maxima: the lowest bin
+            keep, move = best + stay, best.flip(0) + swap
+            sw = move > keep
+            back[t] = torch.where(sw, 1 - torch.arange(2, device=dev).unsqueeze(1), torch.arange(2, device=dev).unsqueeze(1)) * NB \
+                + base + torch.where(sw, off.flip(0), off)
+            delta = torch.where(sw, move, keep) + lo[t]
+            delta = delta - delta.max()
+        state = int(delta.reshape(-1).argmax())  # the first of equal maxima: voiced, the lowest bin
+        walk = back.reshape(T, 2 * NB).cpu().numpy()  # one copy: the walk itself runs on the host
+        path = [state]
+        for t in range(T - 1, 0, -1):
+            state = int(walk[t, state])
+            path.append(state)
+        s = torch.tensor(path[::-1], device=dev)
+        out.append(torch.where(s < NB, centres[s % NB], torch.zeros_like(centres[:1])))
+    return torch.cat(out) if out else obs.new_zeros(0)
+
+
+def pyin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, bins_per_semitone=20, max_transition_rate=35.92,
+         switch_prob=0.01, no_trough_prob=0.01, return_obs=False):
+    """Probabilistic YIN (Mauch & Dixon 2014) of packed utterances, layout and frame counts of ``yin``: the cmnd plane
+    of ``yin`` -> ``pyin_obs`` (pitch candidates of every frame for all YIN thresholds at once, weighted by a Beta(2,
+    18) prior in closed form) -> ``pyin_decode`` (one smooth track per utterance).  Computes in wav's dtype (float64 =
+    the oracle) on wav's device.  -> f0 [R] (bin centres: quantised to 1 / bins_per_semitone semitones, 2.5 cents at
+    the default; 0 = unvoiced), the per-utterance frame counts (host list), voiced_prob [R] and, with
+    ``return_obs``, the plane [R, NB]."""
+    _, frames, tau_min, tau_max, NB, h = pyin_plan(wav, lengths, sr, hop, frame, fmin, fmax, bins_per_semitone,
+                                                   max_transition_rate)
+    _, _, cm = yin(wav, lengths, sr, hop, frame, fmin, fmax, return_cmnd=True)
+    obs, vp = pyin_obs(cm, sr, tau_min, tau_max, fmin, fmax, bins_per_semitone, no_trough_prob)
+    f0 = pyin_decode(obs, vp, frames, sr, hop, fmin, bins_per_semitone, max_transition_rate, switch_prob)
+    return (f0, frames, vp, obs) if return_obs else (f0, frames, vp)

@@ -422,6 +422,145 @@ def bench_yin(out_path, rounds=5, sr=22050, hop=256):
                 f.write(text)
 
 
+def bench_pyin(out_path, rounds=3, sr=22050, hop=256):
+    """``ops.pyin`` (csrc/k_pitch.hip's cmnd plane, then csrc/k_pyin.hip: candidates and Viterbi decode) against the
+    torch reference ``ops.reference.pyin`` on the same GPU tensors and on the host, on the workloads of ``--yin``.  The
+    arms alternate in one process; every call is timed wall-clock between two device synchronisations; the three
+    kernels alone are timed with device events.  The cost of the waveform-level metrics with either tracker is timed
+    on the batch against a noisy copy of itself.  The deviations of the kernels and of the float32 torch reference from
+    the float64 torch reference on the same workloads go to ``pyin_numerics.txt`` beside the table."""
+    import time
+
+    from speakingstyle_amd import ops
+    from speakingstyle_amd.analysis.objective import wave_metrics
+    from speakingstyle_amd.config import load_named
+    from speakingstyle_amd.ops import reference as ref
+
+    dev = torch.device("cuda")
+    pp = load_named("LJSpeech")[0]
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    def med(v):
+        v = sorted(v)
+        return f"{v[len(v) // 2]:10.3f} {v[0]:10.3f} {v[-1]:10.3f}"
+
+    B = hip.PYIN_BINS_PER_THREAD
+    lines = [f"Probabilistic YIN, sr {sr} / hop {hop} / frame 1024 (lags 1 .. 311, 839 bins, band of 101), fp32, "
+             f"{torch.cuda.get_device_name(0)}",
+             f"{rounds} alternating rounds per arm after 1 warm-up round; wall time per call between device syncs (ms);",
+             "kernel rows: device-event time of one launch (3 warm-up launches before each), 20 samples;",
+             f"pyin_viterbi_kernel: {1024 // B} threads per utterance, {B} bins per thread on a sliding window of the "
+             "log-triangle table,", "forward pass and back-trace in one launch", "",
+             f"{'workload':38s} {'arm':>30s} {'median':>10s} {'min':>10s} {'max':>10s}"]
+    num = [f"pYIN kernels (csrc/k_pyin.hip) against the float64 torch reference, {torch.cuda.get_device_name(0)}; the "
+           "workloads of profiles/pyin.txt", "",
+           "ref32 = the float32 torch reference on the same GPU, hip = the kernels; obs dis: frames whose set of non-zero",
+           "bins differs from float64; obs / vp: maximum absolute deviation of the candidate plane / of voiced_prob from",
+           "float64 over the other frames; track dis: frames whose voicing or decoded bin differs from float64", "",
+           f"{'workload':38s} {'frames':>7s} {'voiced':>7s} {'obs dis ref32':>13s} {'obs dis hip':>11s} {'obs ref32':>10s} "
+           f"{'obs hip':>10s} {'vp ref32':>10s} {'vp hip':>10s} {'track dis ref32':>15s} {'track dis hip':>13s}"]
+    for name, wav_h, lens in yin_workloads(sr, hop):
+        wav = wav_h.to(dev)
+        arms = (("hip ops.pyin", lambda: ops.pyin(wav, lens, sr, hop)),
+                ("hip ops.yin", lambda: ops.yin(wav, lens, sr, hop)),
+                ("torch reference, same GPU", lambda: ref.pyin(wav, lens, sr, hop)),
+                ("torch reference, host", lambda: ref.pyin(wav_h, lens, sr, hop)))
+        t = {a: [] for a, _ in arms}
+        for r in range(rounds + 1):
+            for arm, fn in arms:
+                ms = wall(fn)
+                if r >= 1:
+                    t[arm].append(ms)
+        for arm, v in t.items():
+            lines.append(f"{name:38s} {arm:>30s} {med(v)}")
+        a = sorted(t["hip ops.pyin"])
+        for arm in ("torch reference, same GPU", "torch reference, host"):
+            b = sorted(t[arm])
+            lines.append(f"{'':38s} {arm + ' / hip':>30s} {b[len(b) // 2] / a[len(a) // 2]:10.1f}")
+        _, frames, tau_min, tau_max, NB, h = ref.pyin_plan(wav, lens, sr, hop)
+        pack = hip.YinPack(lens, frames, dev)
+        f0 = torch.empty(pack.R, device=dev)
+        cm = torch.empty(pack.R, tau_max + 1, device=dev)
+
+        def launch_yin():
+            hip._check(hip.lib().ssamd_yin(hip._ptr(wav), hip._ptr(pack.off), hip._ptr(pack.n), hip._ptr(pack.rows), pack.R,
+                                           hop, 1024, tau_min, tau_max, float(sr), 0.15, hip._ptr(f0), hip._ptr(cm),
+                                           hip._stream()), "ssamd_yin")
+
+        launch_yin()
+        obs, vp = hip.pyin_obs(cm, sr, tau_min, tau_max)
+        plans = {b: hip.PyinPlan(frames, NB, h, dev, bins_per_thread=b) for b in (2, 4)}
+        plan = plans[B]
+        ws = hip._workspace(dev, plan.ws_floats)
+
+        def launch_obs():
+            hip._check(hip.lib().ssamd_pyin_obs(hip._ptr(cm), pack.R, tau_min, tau_max, float(sr), 71.0, 240.0, NB, 0.01,
+                                                hip._ptr(obs), hip._ptr(vp), hip._stream()), "ssamd_pyin_obs")
+
+        def launch_viterbi(pl=plan):
+            for c0, c1, _ in pl.chunks:
+                hip._check(hip.lib().ssamd_pyin_viterbi(hip._ptr(obs), hip._ptr(vp), hip._ptr(pl.meta[4 * c0:]), c1 - c0,
+                                                        NB, h, pl.bins_per_thread, hip._ptr(pl.tab), math.log(0.99),
+                                                        math.log(0.01), 71.0, 240.0, hip._ptr(ws), hip._ptr(f0),
+                                                        hip._stream()), "ssamd_pyin_viterbi")
+
+        tracks = {}
+        for b, pl in plans.items():  # both forms of the decoder, alternating; they must decode the same track
+            launch_viterbi(pl)
+            tracks[b] = f0.clone()
+        same = torch.equal(tracks[2], tracks[4])
+        tv = {b: [] for b in plans}
+        for _ in range(20):
+            for b, pl in plans.items():
+                tv[b].append(timeit(lambda: launch_viterbi(pl), 1))
+        for kname, fn in (("yin_kernel (with the plane)", launch_yin), ("pyin_obs_kernel", launch_obs)):
+            lines.append(f"{name:38s} {kname:>30s} {med([timeit(fn, 1) for _ in range(20)])}")
+        for b in plans:
+            kname = f"pyin_viterbi_kernel<{b}>" + (" (used)" if b == B else "")
+            lines.append(f"{name:38s} {kname:>30s} {med(tv[b])}")
+        lines.append(f"{'':38s} the two forms decode {'the same track, bitwise' if same else 'DIFFERENT tracks'}")
+        v = sorted(tv[B])
+        lines.append(f"{'':38s} frames: {pack.R} (longest utterance {max(frames)}), back-pointer planes "
+                     f"{sum(c[2] for c in plan.chunks) / 2 ** 20:.1f} MiB in {len(plan.chunks)} launch(es) -> "
+                     f"{1e3 * v[len(v) // 2] / max(frames):.2f} us per frame of the longest utterance at the median")
+        if len(lens) > 1:
+            noisy = (wav + 0.02 * torch.randn(wav.shape, device=dev, generator=torch.Generator(dev).manual_seed(0))).clamp(-1, 1)
+            tw = {k: [] for k in ("yin", "pyin")}
+            for r in range(rounds + 1):
+                for k in tw:
+                    ms = wall(lambda: wave_metrics(noisy, lens, wav, lens, pp, tracker=k))
+                    if r >= 1:
+                        tw[k].append(ms)
+            for k, v in tw.items():
+                lines.append(f"{name:38s} {'wave_metrics, tracker=' + k:>30s} {med(v)}")
+        ref64 = ref.pyin(wav.double(), lens, sr, hop, return_obs=True)
+        got = {"ref32": ref.pyin(wav, lens, sr, hop, return_obs=True), "hip": ops.pyin(wav, lens, sr, hop, return_obs=True)}
+        st = {}
+        for k, (f, _, p, o) in got.items():
+            bad = ((o > 0) != (ref64[3] > 0)).any(1)
+            state = [torch.where(x > 0, torch.round(240 * torch.log2(x.double().clamp(min=1.0) / 71.0)), -torch.ones_like(x.double()))
+                     for x in (f, ref64[0])]
+            st[k] = (int(bad.sum()), float((o.double() - ref64[3])[~bad].abs().max()),
+                     float((p.double() - ref64[2])[~bad].abs().max()), int((state[0] != state[1]).sum()))
+        num.append(f"{name:38s} {pack.R:7d} {int((ref64[0] > 0).sum()):7d} {st['ref32'][0]:13d} {st['hip'][0]:11d} "
+                   f"{st['ref32'][1]:10.3e} {st['hip'][1]:10.3e} {st['ref32'][2]:10.3e} {st['hip'][2]:10.3e} "
+                   f"{st['ref32'][3]:15d} {st['hip'][3]:13d}")
+    for text, path in (("\n".join(lines) + "\n", out_path),
+                       ("\n".join(num) + "\n", out_path and os.path.join(os.path.dirname(os.path.abspath(out_path)),
+                                                                         "pyin_numerics.txt"))):
+        print(text, end="", flush=True)
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=160000)
@@ -436,10 +575,16 @@ def main():
     ap.add_argument("--yin", action="store_true",
                     help="only the pitch arm: the YIN kernel vs the torch reference on the GPU and numpy on the host "
                          "(yin_numerics.txt is written beside --out)")
+    ap.add_argument("--pyin", action="store_true",
+                    help="only the probabilistic-YIN arm: ops.pyin vs the torch reference on the GPU and on the host, "
+                         "kernel-only times, wave_metrics with either tracker (pyin_numerics.txt is written beside --out)")
     ap.add_argument("--out", default=None,
-                    help="default: profiles/griffin_lim.txt, profiles/dtw.txt, profiles/align.txt, profiles/yin.txt")
+                    help="default: profiles/griffin_lim.txt, profiles/dtw.txt, profiles/align.txt, profiles/yin.txt, "
+                         "profiles/pyin.txt")
     args = ap.parse_args()
     prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    if args.pyin:
+        return bench_pyin(args.out or os.path.join(prof, "pyin.txt"))
     if args.yin:
         return bench_yin(args.out or os.path.join(prof, "yin.txt"))
     if args.align:
