@@ -152,6 +152,18 @@ def build_dtw_selftest():
     return exe
 
 
+def build_k256_selftest():
+    """The K = 256 GEMM work split (csrc/k256_split.h) as plain host code under ASan+UBSan: returns the
+    self-test executable (csrc/selftest_k256_split.cpp) in build/sanitize/."""
+    out_dir = os.path.join(ROOT, "build", "sanitize")
+    os.makedirs(out_dir, exist_ok=True)
+    test = os.path.join(HERE, "selftest_k256_split.cpp")
+    exe = os.path.join(out_dir, "selftest_k256_split")
+    if _stale(exe, [test, os.path.join(HERE, "k256_split.h")]):
+        _run(["g++", "-O1", "-g", "-std=c++17", "-I", HERE] + SANITIZERS["asan"] + ["-o", exe, test])
+    return exe
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 4))

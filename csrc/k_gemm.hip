@@ -23,6 +23,7 @@
 // that share an A panel run on one XCD's L2.
 #include <mutex>
 #include "common.h"
+#include "k256_split.h"
 #include <type_traits>
 
 namespace {
@@ -1451,6 +1452,175 @@ __global__ void __launch_bounds__(NT3, 1) conv_gemm_big64_kernel(const bf16_t* _
   big64_tile<OUT_F32, FASTK, PACKED, BUF, EPIM, STG>(X, W, bias, aux, resid, lens, Yv, g, act, ldy, ex, blockIdx.x);
 }
 
+// ----------------------------------------------------------------------------
+// Weight-stationary GEMM for K = 256 (Linear layers of the FFT blocks: Cin = 256, ks = 1, N % 256 == 0):
+//   Y[M, N] = bf16( X[M, 256] . Wt[N, 256]^T (+ bias) ) (* ReLU bitmask)
+// A 256x256 tile kernel at K = 256 is four k-steps between an exposed prologue and an exposed epilogue, and
+// every tile fetches its 128 KiB weight slice again.  Here a block owns one 256-column slice for its whole
+// life: each of its 8 waves (2 along m x 4 along n) keeps the 64 columns x 256 k it multiplies in 128
+// VGPRs (registers, not LDS: 128 KiB of weights would leave no room for a row ring), and the block
+// streams a contiguous range of 64-row chunks past them:
+//   * A chunks (32 KiB: four [64 rows][64 k] swz128 images) arrive by LDS-DMA into a 3-stage ring, two
+//     chunks ahead of the MFMAs; the chunk's ReLU-mask bytes (2 KiB) ride along as 4-byte LDS-DMA, so no
+//     VGPR-destination load is ever in flight inside the loop;
+//   * per chunk: 64 MFMAs per wave -> bf16 staging tile (ct_woff / ct_read) -> 16-B-per-lane stores of
+//     whole 512-B row pieces, which drain under the next chunk's MFMAs;
+//   * counted waits only.  Every thread issues exactly D = 4 (+1 mask) DMA and 4 store instructions per
+//     chunk, unconditionally -- rows past M and chunks past the range are out of the buffer descriptors'
+//     range (loads land zeros, stores are dropped) -- so "chunk k+1 has landed" is vmcnt(8 + D): younger
+//     than its DMA are only stores(k-1), DMA(k+2) and stores(k).
+// Grid: ng = N / 256 column groups x nb blocks (k256_split.h); the ng blocks that read the same rows are
+// consecutive remapped ids, i.e. on one XCD.  Blocks never communicate.
+// Bitwise identical to the big64 / ring kernels: same MFMA, same operand order, k ascending over the eight
+// 32-wide blocks with chunk c = kk * 4 + (lane >> 4), and acc + bias -> bf16 -> mask.
+// ----------------------------------------------------------------------------
+constexpr int K2_STAGES = 3;
+constexpr int K2_A_BYTES = K256_ROWS * 256 * 2;                // 32 KiB per stage
+constexpr int K2_CT_OFF = K2_STAGES * K2_A_BYTES;              // staging tile [64][528 B]
+constexpr int K2_MK_OFF = K2_CT_OFF + K256_ROWS * 528;         // mask ring [3][64 rows][32 B]
+constexpr int K2_MK_BYTES = K256_ROWS * 32;
+constexpr int K2_LDS = K2_MK_OFF + K2_STAGES * K2_MK_BYTES;    // 135 KiB
+
+typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void k2_barrier() {  // LDS-only: in-flight DMA and stores cross it
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" ::: "memory");
+}
+
+template <bool MASK, bool HB>
+__global__ void __launch_bounds__(NT3, 1) conv_gemm_k256_kernel(const bf16_t* __restrict__ X,
+                                                                const bf16_t* __restrict__ W,
+                                                                const float* __restrict__ bias,
+                                                                const unsigned char* __restrict__ mask,
+                                                                bf16_t* __restrict__ Y, int M, int N, int nb) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int ng = N >> 8;
+  const int T = xcd_remap(blockIdx.x, gridDim.x);
+  const int r = T / ng, cg = T - r * ng;
+  if (r >= nb) return;
+  int c0, c1;
+  k256_chunk_range(k256_chunks(M), nb, r, &c0, &c1);
+  const int nch = c1 - c0;
+  if (nch <= 0) return;  // a block with no rows
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;  // 2 x 4 waves of 32 (m) x 64 (n) per chunk
+  const int n0 = cg * 256;
+
+  // out-of-range offsets (rows >= M) read zeros / drop the store: no per-row predicate anywhere
+  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, M * 512, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc((void*)Y, 0, M * N * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rM =
+      __builtin_amdgcn_make_buffer_rsrc((void*)(MASK ? mask : (const unsigned char*)X), 0, MASK ? M * (N >> 3) : 0,
+                                        0x00020000);
+  // DMA: a wave instruction fills 8 rows x 128 B of one k slab; wave w owns rows 8 w .. 8 w + 7 of every slab
+  const int arow = wave * 8 + (lane >> 3);
+  const int avo = (arow * 256 + (((lane & 7) ^ ((arow >> 1) & 7)) << 3)) * 2;
+  const int mvo = arow * (N >> 3) + cg * 32 + (lane & 7) * 4;
+  auto issue = [&](int k) {  // chunk c0 + k -> stage k % 3 (always 4 (+1) instructions)
+    const int st = k % K2_STAGES;
+    const int m0 = (c0 + k) * K256_ROWS;
+    char* As = smem + st * K2_A_BYTES + wave * 1024;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) buf_lds16(rA, avo + m0 * 512 + i * 128, 0, As + i * 8192);
+    if constexpr (MASK)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(
+          rM, (__attribute__((address_space(3))) void*)(smem + K2_MK_OFF + st * K2_MK_BYTES + wave * 256), 4,
+          mvo + m0 * (N >> 3), 0, 0, 0);
+  };
+  issue(0);
+  issue(1);
+  // the wave's weights: fb[kb][j] = columns n0 + 64 wn + 16 j + (lane & 15), k = 32 kb + 8 (lane >> 4) .. + 7
+  short8 fb[8][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bf16_t* wr = W + (long)(n0 + wn * 64 + j * 16 + (lane & 15)) * 256 + (lane >> 4) * 8;
+#pragma unroll
+    for (int kb = 0; kb < 8; ++kb) fb[kb][j] = *reinterpret_cast<const short8*>(wr + kb * 32);
+  }
+  float4 bv[4];
+  if constexpr (HB) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bv[j] = *reinterpret_cast<const float4*>(bias + n0 + wn * 64 + j * 16 + 4 * (lane >> 4));
+  }
+  // weights and bias are in registers before the loop (their one wait also retires chunks 0 and 1): a load
+  // result first used inside the loop would make the compiler drain the ring there, every chunk
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int kb = 0; kb < 8; ++kb)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(fb[kb][j]));
+  if constexpr (HB) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(bv[j].x), "+v"(bv[j].y), "+v"(bv[j].z), "+v"(bv[j].w));
+  }
+  k2_barrier();
+
+  char* Ct = smem + K2_CT_OFF;
+  const int c = tid & 31, r0 = tid >> 5;  // store phase: 16-B column chunk c of rows r0 + 16 it
+  const int yvo = (r0 * N + n0 + c * 8) * 2;
+  for (int k = 0; k < nch; ++k) {
+    // chunk k is in stage k % 3 and visible; stage (k + 2) % 3 was last read in iteration k - 1
+    issue(k + 2);
+    const int st = k % K2_STAGES;
+    const char* As = smem + st * K2_A_BYTES;
+    float4v acc[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = (float4v){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < 8; ++kb) {
+      const int cc = (kb & 1) * 4 + (lane >> 4);
+      short8 fa[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        fa[i] = *reinterpret_cast<const short8*>(As + (kb >> 1) * 8192 + swz128(wm * 32 + i * 16 + (lane & 15), cc));
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kb][j], fa[i], acc[i][j], 0, 0, 0);
+    }
+    // accumulators -> bf16 staging tile (its readers of iteration k - 1 passed the last barrier)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int ml = wm * 32 + i * 16 + (lane & 15);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int nl = wn * 64 + j * 16 + 4 * (lane >> 4);
+        float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+        if constexpr (HB) {
+          v[0] += bv[j].x; v[1] += bv[j].y; v[2] += bv[j].z; v[3] += bv[j].w;
+        }
+        short4v o;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = (short)f2bf(v[q]);
+        *reinterpret_cast<short4v*>(Ct + ct_woff(ml, nl)) = o;
+      }
+    }
+    k2_barrier();
+    const int ybase = (c0 + k) * K256_ROWS * N * 2;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int rr = r0 + 16 * it;
+      short8 v = ct_read(Ct, rr, c);
+      if constexpr (MASK) {
+        const unsigned mb = *reinterpret_cast<const unsigned char*>(smem + K2_MK_OFF + st * K2_MK_BYTES + rr * 32 + c);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = (short)f2bf((mb >> q) & 1u ? bf2f((bf16_t)v[q]) : 0.f);
+      }
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4v, v), rY, yvo + ybase + it * 16 * N * 2, 0, 0);
+    }
+    // chunk k + 1 landed: 4 stores (k - 1), the DMA of chunk k + 2 and 4 stores (k) may stay in flight
+    if constexpr (MASK) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+    k2_barrier();
+  }
+}
+
 
 // ----------------------------------------------------------------------------
 // Weight gradient.  Tile: 128 (n = cout) x 128 (k = tap*Cin + cin), reduction over
@@ -2682,6 +2852,14 @@ static int g_gemm_bnh_stg = 1;   // the BatchNorm-backward-head data gradient on
 SSAMD_API void ssamd_gemm_set_bnh_stg(int v) { g_gemm_bnh_stg = v; }
 SSAMD_API void ssamd_gemm_set_mask_pre(int v) { g_gemm_mask_pre = v; }
 SSAMD_API void ssamd_gemm_set_stg(int v) { g_gemm_stg = v; }
+// weight-stationary K = 256 kernel (conv_gemm_k256_kernel): -1 auto (the measured rule in conv_gemm_impl), 0 off,
+// 1 on wherever the shape qualifies regardless of M
+static int g_gemm_k256 = -1;
+static int g_k256_min_rows = 28672;  // N = 512 / 768: the measured crossover lies between 14336 and 28672 rows
+static int g_k256_blocks = 0;  // > 0: grid budget instead of the device's CUs (tests: many chunks per block)
+SSAMD_API void ssamd_gemm_set_k256(int v) { g_gemm_k256 = v; }
+SSAMD_API void ssamd_gemm_set_k256_blocks(int v) { g_k256_blocks = v; }
+static int device_cus();
 
 // every byte offset of the descriptors must stay below the out-of-range marker 0x80000000
 static bool big64_buf_ok(const ConvGeom& g) {
@@ -2809,6 +2987,47 @@ static int conv_gemm_impl(const bf16_t* X, const bf16_t* W, const float* bias, c
                          act, out_f32, Y, ex.acc, ex.y2, ex.scale, ex.post_act);
       return (int)hipGetLastError();
     }
+  }
+  // K = 256 Linear layers (QKV, attention fc and its data gradient, the w_2 data gradient with its ReLU
+  // bitmask): the weight-stationary streaming kernel, one block per CU.  Only the epilogue forms the training
+  // step uses at K = 256 (bias, mask_in, bf16 out, ldy == N); everything else stays on the tile kernels.
+  // Rows: every byte offset of its descriptors (two chunks of read-ahead included) stays below 2^31.
+  // Auto rule, measured against the kernel each shape ran on before (tools/bench_kernels.py --k256, 5 interleaved
+  // rounds, routed only where every round of the new kernel beat every round of the old;
+  // profiles/k256_stream.txt; us old -> new):
+  //   N >= 1024 (ReLU-mask dgrad)  from 2048 rows: 100352 rows 147 -> 80, 14336 rows 22.4 -> 21.5, 2048 19.5 -> 12.3
+  //   N = 512 / 768 (QKV)          from 28672 rows: 100352 rows 77 -> 55, 28672 26.6 -> 23; 8192 / 14336 rows LOSE
+  //                                (13.8 -> 15.5, 15.8 -> 18.3: 3 groups x 85 blocks of ~3 chunks, prologue-bound)
+  //   N = 256 (fc fwd / dgrad)     <= 64 tiles, where the 256x128 ring ran (14336 rows 14.6 -> 13.1, 2048 13.1 -> 10.9),
+  //                                and from 1.5 waves of 256-row tiles (100352 rows 29.3 -> 27.7, 30.0 -> 28.6 in
+  //                                a second session); up to one wave the balanced 256x256 tiles win (28672 rows
+  //                                13.8 -> 16.0, 50176 15.3 -> 19.4), between 1 and 1.5 waves it is mixed (69632 rows
+  //                                26.5 -> 23.5 every round, 81920 rows 27.7 -> 27.3 with one round behind)
+  // Below 2048 rows nothing was measured (the skinny kernel takes <= 1024).
+  const int k256_tiles = (g.M + BG - 1) / BG;
+  const bool k256_auto = g_gemm_variant < 0 && g.M >= 2048 &&
+                         (N >= 1024 || (N >= 512 && g.M >= g_k256_min_rows) ||
+                          (N == 256 && (k256_tiles <= 64 || 2 * k256_tiles >= 3 * device_cus())));
+  if (g_gemm_k256 != 0 && ks == 1 && Cin == 256 && N >= 256 && N % 256 == 0 && !out_f32 && !aux && !resid && !lens &&
+      !rinfo && !bnh && ksplit == 0 && act == 0 && ldy == N && reg && !ex.acc && !ex.y2 && !ex.post_act &&
+      ex.scale == 1.f && !ex.mask_out && !ex.bn_stats && !ex.bn_part &&
+      ((long)g.M + 4 * K256_ROWS) * (N > 256 ? N : 256) * 2 < (1L << 31) &&
+      (g_gemm_k256 > 0 || k256_auto)) {
+    static bool k2_set = false;
+    if (!k2_set) {
+      allow_lds(conv_gemm_k256_kernel<false, false>, K2_LDS);
+      allow_lds(conv_gemm_k256_kernel<false, true>, K2_LDS);
+      allow_lds(conv_gemm_k256_kernel<true, false>, K2_LDS);
+      allow_lds(conv_gemm_k256_kernel<true, true>, K2_LDS);
+      k2_set = true;
+    }
+    const int ng = N / 256;
+    const int nb = k256_blocks_per_group(g_k256_blocks > 0 ? g_k256_blocks : device_cus(), ng, k256_chunks(g.M));
+    auto kfn = ex.mask_in ? (bias ? conv_gemm_k256_kernel<true, true> : conv_gemm_k256_kernel<true, false>)
+                          : (bias ? conv_gemm_k256_kernel<false, true> : conv_gemm_k256_kernel<false, false>);
+    hipLaunchKernelGGL(kfn, dim3(nb * ng), dim3(NT3), K2_LDS, s, X, W, bias, ex.mask_in, reinterpret_cast<bf16_t*>(Y),
+                       g.M, N, nb);
+    return (int)hipGetLastError();
   }
   if (bnh) {  // BatchNorm-backward head (EpiX aliases: acc = bn_h, ln_w = stats, mean = partials): big64 only
     if (N < 256 || (N % 8) || ldy != N || out_f32 || !reg || act != 0 || ex.post_act == 2 || aux || resid || lens || !ex.acc ||

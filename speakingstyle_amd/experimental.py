@@ -48,6 +48,17 @@ def _tristate(v):
     return s
 
 
+def _auto_int(v):
+    """-1 / auto, 0, 1 (a kernel-library tristate, kept as the integer its setter takes)."""
+    s = str(v).strip().lower()
+    if s == "auto":
+        return -1
+    i = int(s)
+    if i not in (-1, 0, 1):
+        raise ValueError(f"expected -1 (auto) / 0 / 1, got {v!r}")
+    return i
+
+
 def _pos_int(v):
     i = int(v)
     if i <= 0:
@@ -79,6 +90,8 @@ KNOBS: Dict[str, tuple] = {
     "gemm_stg": (True, _bool, "staggered 8-phase main loop of the 256x256 GEMM for K >= 512 (+0.7 % LJSpeech)"),
     "gemm_mask_pre": (True, _bool, "ReLU-mask data gradient with its mask bytes prefetched before the main loop"),
     "gemm_bnh_stg": (True, _bool, "PostNet BatchNorm-backward-head data gradient on the staggered main loop"),
+    "gemm_k256": (-1, _auto_int, "weight-stationary streaming kernel for the K = 256 Linear GEMMs: 0 off, 1 wherever "
+                                 "the shape qualifies, -1 / auto from its measured row threshold"),
     "gemm_ring_maxk": (0, int, "GEMMs with K <= this on the 256x128 ring kernel at any tile count (0: only <= 64 "
                                "big tiles)"),
     "gemm_ring_maxn": (256, int, "widest N of gemm_ring_maxk"),
@@ -101,7 +114,8 @@ KNOBS: Dict[str, tuple] = {
 KERNEL_SWITCHES = {"gemm_stg": "ssamd_gemm_set_stg", "gemm_mask_pre": "ssamd_gemm_set_mask_pre",
                    "gemm_bnh_stg": "ssamd_gemm_set_bnh_stg", "gemm_ring_maxk": "ssamd_gemm_set_ring_maxk",
                    "gemm_ring_maxn": "ssamd_gemm_set_ring_maxn", "gemm_skinny": "ssamd_gemm_set_skinny",
-                   "gemm_skinny_maxm": "ssamd_gemm_set_skinny_maxm", "attn_xcd": "ssamd_attn_set_xcd"}
+                   "gemm_skinny_maxm": "ssamd_gemm_set_skinny_maxm", "attn_xcd": "ssamd_attn_set_xcd",
+                   "gemm_k256": "ssamd_gemm_set_k256"}
 
 _values: Dict[str, Any] = {}
 _parsed = [False]

@@ -59,6 +59,8 @@ _SIGS = {
     "ssamd_gemm_set_buf": [I],
     "ssamd_gemm_set_stg": [I],
     "ssamd_gemm_set_mask_pre": [I],
+    "ssamd_gemm_set_k256": [I],
+    "ssamd_gemm_set_k256_blocks": [I],
     "ssamd_gemm_set_bnh_stg": [I],
     "ssamd_bn_set_dz_cfg": [I, I],
     "ssamd_wgrad_set_pp": [I],

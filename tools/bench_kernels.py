@@ -561,6 +561,54 @@ def bench_pyin(out_path, rounds=3, sr=22050, hop=256):
                 f.write(text)
 
 
+def bench_k256(out_path, rounds=5, iters=20):
+    """The K = 256 Linear GEMMs of the training step (QKV forward, attention fc forward / data gradient, the w_2
+    data gradient with its ReLU bitmask): the tile kernels (gemm_k256 = 0) against the weight-stationary
+    streaming kernel (= 1) in one process, arms interleaved, `rounds` rounds of `iters` launches each.  Decoder
+    rows (100 352), encoder rows (14 336) and a row sweep for the crossover.  The inputs rotate over four
+    copies so that a launch does not find its rows in the Infinity Cache from the launch before."""
+    dev = "cuda"
+    lib = hip.lib()
+    lines = ["K = 256 GEMMs, us per launch: tile kernels (old) vs weight-stationary streaming kernel (new); "
+             f"{rounds} interleaved rounds x {iters} launches; floor = bytes / 6.2 TB/s",
+             f"{'rows':>7} {'N':>5} {'epilogue':>8} {'old min..max':>15} {'new min..max':>15} {'new/old':>8} "
+             f"{'floor':>6}  verdict"]
+    print(lines[0] + "\n" + lines[1], flush=True)
+    torch.manual_seed(0)
+    for M in (100352, 14336, 81920, 69632, 50176, 28672, 20480, 8192, 4096, 2048):
+        xs = [(torch.randn(1, M, 256, device=dev) / 16).to(torch.bfloat16) for _ in range(4)]
+        for N, epi in ((256, "-"), (768, "bias"), (1024, "mask")):
+            w = (torch.randn(N, 1, 256, device=dev) / 16).to(torch.bfloat16)
+            b = torch.randn(N, device=dev) if epi == "bias" else None
+            mk = torch.randint(0, 256, (M, N // 8), device=dev, dtype=torch.uint8) if epi == "mask" else None
+            it = [0]
+
+            def run():
+                it[0] += 1
+                x = xs[it[0] & 3]
+                if mk is not None:
+                    return hip.conv_gemm_mask_raw(x, w, None, 1, M, 256, 1, 0, N, 0, mask_in=mk)
+                return hip.conv_gemm_raw(x, w, b, 1, M, 256, 1, 1, 0, N, 0)
+
+            t = {0: [], 1: []}
+            try:
+                for _ in range(rounds):
+                    for arm in (0, 1):
+                        lib.ssamd_gemm_set_k256(arm)
+                        t[arm].append(timeit(run, iters) * 1e3)
+            finally:
+                lib.ssamd_gemm_set_k256(-1)
+            floor = (M * 512 + M * N * 2 + N * 512 + (M * N // 8 if mk is not None else 0)) / 6.2e6
+            wins = max(t[1]) < min(t[0])
+            line = (f"{M:7d} {N:5d} {epi:>8} {min(t[0]):7.1f}..{max(t[0]):<6.1f} {min(t[1]):7.1f}..{max(t[1]):<6.1f} "
+                    f"{sorted(t[1])[rounds // 2] / sorted(t[0])[rounds // 2]:8.3f} {floor:6.1f}  "
+                    f"{'new wins every round' if wins else 'no clear win'}")
+            lines.append(line)
+            print(line, flush=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=160000)
@@ -578,11 +626,15 @@ def main():
     ap.add_argument("--pyin", action="store_true",
                     help="only the probabilistic-YIN arm: ops.pyin vs the torch reference on the GPU and on the host, "
                          "kernel-only times, wave_metrics with either tracker (pyin_numerics.txt is written beside --out)")
+    ap.add_argument("--k256", action="store_true",
+                    help="only the K = 256 Linear GEMMs: tile kernels vs the weight-stationary streaming kernel")
     ap.add_argument("--out", default=None,
                     help="default: profiles/griffin_lim.txt, profiles/dtw.txt, profiles/align.txt, profiles/yin.txt, "
-                         "profiles/pyin.txt")
+                         "profiles/pyin.txt, profiles/k256_shapes.txt")
     args = ap.parse_args()
     prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    if args.k256:
+        return bench_k256(args.out or os.path.join(prof, "k256_shapes.txt"), iters=args.iters)
     if args.pyin:
         return bench_pyin(args.out or os.path.join(prof, "pyin.txt"))
     if args.yin:
