@@ -84,11 +84,11 @@ def run(args):
     if args.rb_half and cuda:
         from speakingstyle_amd.ops import hip
 
-        hip.lib().ssamd_resblock_set_tall(2)
+        hip.set_resblock_tall(2)
     if args.rb_regular and cuda:
         from speakingstyle_amd.ops import hip
 
-        hip.lib().ssamd_resblock_set_tall(0)
+        hip.set_resblock_tall(0)
     if args.whole_skip:
         from speakingstyle_amd.models import hifigan as _H
 

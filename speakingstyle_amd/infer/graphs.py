@@ -41,6 +41,8 @@ import time
 
 import torch
 
+from ..ops import weights
+
 
 def _multi_copy(pairs) -> bool:
     from ..ops import hip
@@ -124,7 +126,7 @@ class SynthGraphs:
         with torch.cuda.graph(g, pool=self.pool, stream=self.stream):
             out = fn()
         torch.cuda.synchronize()
-        self.wgen = hip._wgen
+        self.wgen = weights.generation()
         self.stats["captures"] += 1
         self.stats["capture_s"] += time.perf_counter() - t0
         return g, out
@@ -136,9 +138,7 @@ class SynthGraphs:
     def _check_weights(self):
         """The graphs replay kernels on the weight images they were captured with: drop them all once the weights
         have been declared changed (``hip.bump_weight_generation``); the next calls warm and capture again."""
-        from ..ops import hip
-
-        if self.wgen is not None and self.wgen != hip._wgen:
+        if self.wgen is not None and self.wgen != weights.generation():
             torch.cuda.synchronize()
             self.g2.clear()
             self.g1.clear()

@@ -23,6 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ..ops.weights import DerivedCache
 from ..config import style_mode
 from ..text.symbols import symbols
 from .layers import FFTBlock, FiLM, LinearNorm, PostNet, fused_param_groups
@@ -33,21 +34,17 @@ def _pe_param(n_position: int, d: int) -> nn.Parameter:
     return nn.Parameter(ops.sinusoid_table(n_position, d).unsqueeze(0), requires_grad=False)
 
 
-_PE_CAST = ops.IdCache()  # positional table -> ((dtype, version, address), cast copy)
+_pe_cast = DerivedCache()  # positional table -> its copy in the dtype last asked for
 
 
 def positional_rows(pe_param: torch.Tensor, length: int, d: int, device, dtype=None) -> torch.Tensor:
     """First ``length`` sinusoid rows; beyond the stored table (eval on long
     inputs, reference ``transformer/Models.py:82-87``) they are generated.  ``dtype``: the rows in that dtype,
-    from a per-dtype copy of the (constant, non-trainable) table made once."""
+    from a copy of the (constant, non-trainable) table in that dtype, cached per version and weight generation."""
     if length <= pe_param.shape[1]:
         if dtype is None or dtype == pe_param.dtype:
             return pe_param[0, :length]
-        hit = _PE_CAST.get(pe_param)
-        if hit is None or hit[0] != (dtype, pe_param._version, pe_param.data_ptr()):
-            hit = ((dtype, pe_param._version, pe_param.data_ptr()), pe_param.detach()[0].to(dtype).contiguous())
-            _PE_CAST.put(pe_param, hit)
-        return hit[1][:length]
+        return _pe_cast.get(pe_param, (pe_param,), lambda: pe_param[0].to(dtype).contiguous(), extra=dtype)[:length]
     t = ops.sinusoid_table(length, d, device=device)
     return t if dtype is None else t.to(dtype)
 

@@ -31,6 +31,9 @@ import torch.nn.functional as F
 from torch.nn.utils import spectral_norm, weight_norm
 
 from .. import ops
+from ..ops.weights import DerivedCache
+
+_ups_images = DerivedCache()  # Generator: ups[i] weight -> _ups_image(i)
 
 LRELU_SLOPE = 0.1
 # whole-ResBlock kernel for the narrow stages (False: one fused kernel per layer pair; A/B + tests)
@@ -430,23 +433,19 @@ class Generator(nn.Module):
 
     def _ups_image(self, i):
         """(fp32 [s*Cout, Cin, 3] weight, bf16 [s*Cout][3][Cin] operand image, tiled bias) of
-        upsampling layer i as one 3-tap convolution (``convT_as_conv3``), cached per weight version."""
+        upsampling layer i as one 3-tap convolution (``convT_as_conv3``; None for another geometry), cached per
+        version and weight generation."""
         up = self.ups[i]
         w = _w(up)
-        key = (w.data_ptr(), w._version, None if up.bias is None else up.bias._version)
-        cache = self.__dict__.setdefault("_ups_cache", {})
-        hit = cache.get(i)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        wu = convT_as_conv3(w.detach().float(), up.stride[0], up.padding[0])
-        if wu is None:
-            val = None
-        else:
-            s = up.stride[0]
-            bt = None if up.bias is None else up.bias.detach().float().repeat(s).contiguous()
-            val = (wu, wu.permute(0, 2, 1).to(torch.bfloat16).contiguous(), bt)
-        cache[i] = (key, val)
-        return val
+
+        def build():
+            wu = convT_as_conv3(w.float(), up.stride[0], up.padding[0])
+            if wu is None:
+                return None
+            bt = None if up.bias is None else up.bias.float().repeat(up.stride[0]).contiguous()
+            return (wu, wu.permute(0, 2, 1).to(torch.bfloat16).contiguous(), bt)
+
+        return _ups_images.get(w, (w, up.bias), build)
 
     def _infer_hip(self, mel, int16_scale):
         """GPU inference: every op is a HIP kernel, every activation / bias / accumulate sits in a
@@ -502,7 +501,8 @@ class Generator(nn.Module):
     def packable(self) -> bool:
         """Every upsampler has the 3-tap form and conv_post the VALU kernel: ``infer_packed`` applies."""
         c_last = self.h.upsample_initial_channel // 2 ** self.num_upsamples
-        return c_last in (8, 32) and all(self._ups_image(i) is not None for i in range(self.num_upsamples))
+        return c_last in (8, 32) and all(_conv3_form(up.kernel_size[0], up.stride[0], up.padding[0])
+                                         for up in self.ups)
 
     def _packed_geoms(self, lens):
         """Every (rate, tile height) the tiled kernels of ``infer_packed`` ask for at these frame lengths."""
@@ -633,6 +633,11 @@ def ref_conv_post(x, w, b):
     return ops.ref.conv1d(x.float(), w.float(), None if b is None else b.float(), 3, 1, None)
 
 
+def _conv3_form(K: int, s: int, pad: int) -> bool:
+    """The ConvTranspose1d geometries ``convT_as_conv3`` covers (asked per call by ``Generator.packable``)."""
+    return K == s + 2 * pad and 0 <= pad <= s
+
+
 def convT_as_conv3(w, stride: int, pad: int):
     """ConvTranspose1d weight [Cin, Cout, K] -> an ordinary 3-tap conv weight [stride*Cout, Cin, 3].
 
@@ -645,7 +650,7 @@ def convT_as_conv3(w, stride: int, pad: int):
     pass.  Returns None for other geometries."""
     Cin, Cout, K = w.shape
     s = int(stride)
-    if K != s + 2 * pad or pad > s or pad < 0:
+    if not _conv3_form(K, s, pad):
         return None
     wu = w.new_zeros(s, Cout, Cin, 3)
     for r in range(s):

@@ -16,6 +16,28 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ..ops.weights import DerivedCache
+
+_folded = DerivedCache()  # first conv weight of a conv + BatchNorm stack -> folded_batchnorm()
+
+
+def folded_batchnorm(pairs, finish):
+    """Per (conv, BatchNorm) pair ``finish(conv, W * s, b * s + t)`` with s = gamma / sqrt(running_var + eps), t =
+    beta - running_mean * s: the conv followed by eval BatchNorm as one conv.  Cached per parameter / buffer version
+    and weight generation under the first conv weight (``_folded``: not on a module, never in a state dict)."""
+    pairs = list(pairs)
+
+    def build():
+        out = []
+        for conv, bn in pairs:
+            s = bn.weight.float() * torch.rsqrt(bn.running_var.float() + bn.eps)
+            t = bn.bias.float() - bn.running_mean.float() * s
+            b = conv.bias.float() if conv.bias is not None else torch.zeros_like(s)
+            out.append(finish(conv, conv.weight.float() * s.view(-1, *([1] * (conv.weight.dim() - 1))), b * s + t))
+        return out
+
+    return _folded.get(pairs[0][0].weight, [t for conv, bn in pairs for t in (
+        conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)], build)
 
 FiLMParams = Optional[Tuple[torch.Tensor, torch.Tensor]]  # (gamma [B,C], beta [B,C])
 
@@ -195,25 +217,6 @@ class PostNet(nn.Module):
         return h
 
     def folded(self):
-        """Per layer (W * s, b * s + t) with s = gamma / sqrt(running_var + eps), t = beta - running_mean * s:
-        conv followed by eval BatchNorm as one conv.  Cached per parameter / buffer version (not registered,
-        so never in the state dict)."""
-        ts = []
-        for conv, bn in self.convolutions:
-            ts += [conv.conv.weight, conv.conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        key = tuple((t.data_ptr(), t._version) for t in ts if t is not None)
-        hit = self.__dict__.get("_fold")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        out = []
-        with torch.no_grad():
-            for conv, bn in self.convolutions:
-                w = conv.conv.weight.detach().float()
-                s = bn.weight.detach().float() * torch.rsqrt(bn.running_var.float() + bn.eps)
-                t = bn.bias.detach().float() - bn.running_mean.float() * s
-                b = conv.conv.bias.detach().float() if conv.conv.bias is not None else torch.zeros_like(s)
-                wf = nn.Parameter((w * s.view(-1, *([1] * (w.dim() - 1)))).to(conv.conv.weight.dtype),
-                                  requires_grad=False)
-                out.append((wf, (b * s + t).contiguous()))
-        self.__dict__["_fold"] = (key, out)
-        return out
+        """Per layer (folded weight as a Parameter, so that its operand image is cached too; folded bias)."""
+        return folded_batchnorm(((c.conv, bn) for c, bn in self.convolutions), lambda c, w, b: (
+            nn.Parameter(w.to(c.weight.dtype), requires_grad=False), b.contiguous()))

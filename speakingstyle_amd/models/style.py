@@ -19,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .layers import ConvHolder, FFTBlock, LinearNorm
+from .layers import ConvHolder, FFTBlock, LinearNorm, folded_batchnorm
 
 
 class ReferenceEncoder(nn.Module):
@@ -166,26 +166,10 @@ class GlobalStyleTokens(nn.Module):
         return ops.gru_last(x, self.gru, ((mel_lens - 1) >> n).clamp(0, T - 1))
 
     def folded_convs(self):
-        """Per layer the ``ops.conv2d_s2_prepare`` operand of (W * s, b * s + t), s = gamma / sqrt(running_var +
-        eps), t = beta - running_mean * s: Conv2d + eval BatchNorm2d as one conv.  Cached per parameter / buffer
-        version (not registered: never in the state dict); on the GPU the weight images are built here once
-        instead of per call (batch-1 serving is launch-bound)."""
-        ts = []
-        for conv, bn in zip(self.convs, self.bns):
-            ts += [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        key = tuple((t.data_ptr(), t._version, t.device) for t in ts if t is not None)
-        hit = self.__dict__.get("_fold")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        out = []
-        with torch.no_grad():
-            for conv, bn in zip(self.convs, self.bns):
-                s = bn.weight.float() * torch.rsqrt(bn.running_var.float() + bn.eps)
-                t = bn.bias.float() - bn.running_mean.float() * s
-                b = conv.bias.float() if conv.bias is not None else torch.zeros_like(s)
-                out.append(ops.conv2d_s2_prepare(conv.weight.float() * s.view(-1, 1, 1, 1), b * s + t))
-        self.__dict__["_fold"] = (key, out)
-        return out
+        """Per layer the ``ops.conv2d_s2_prepare`` operand of Conv2d + eval BatchNorm2d as one conv
+        (``folded_batchnorm``); on the GPU the weight images are built here once instead of per call (batch-1
+        serving is launch-bound)."""
+        return folded_batchnorm(zip(self.convs, self.bns), lambda c, w, b: ops.conv2d_s2_prepare(w, b))
 
     def token_bank(self):
         """Keys / values of the style-token bank, [heads, n_tok, token_size/heads] each."""

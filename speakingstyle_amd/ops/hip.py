@@ -24,6 +24,7 @@ from typing import Optional
 import torch
 
 from . import gradslots
+from .weights import DerivedCache, bump_generation, generation
 from . import reference as ref
 
 _LIB_PATH = os.environ.get("SSAMD_KERNEL_LIB") or os.path.join(  # override: A/B runs of another build
@@ -287,21 +288,29 @@ def _need(t, dtype, name):
 
 
 # ------------------------------------------------------------------------ weight images
-# bf16 operand images of fp32 master weights, keyed by (parameter, layout).  An image is
-# valid for one (param._version, weight generation) pair: the fused Adam kernel writes the
-# arena through raw pointers (torch's version counters do not see it), so the optimizer
-# calls ``bump_weight_generation()``; the first stale lookup afterwards refreshes EVERY
-# registered image in one batched ``weight_prep`` launch instead of ~2 cast kernels per weight.
-_wcache = {}          # key -> [version, generation, weakref(param), image, mode, src_ptr]
-_wgen = 0
+# bf16 operand images of fp32 master weights, keyed by (parameter, layout).  An image is valid for one
+# (param._version, weight generation) pair.  The generation lives in ``ops/weights.py``: whoever writes
+# parameters through raw pointers (the fused Adam step, DDP, style tuning) bumps it, since torch's version
+# counters do not see such writes.  Three kinds of cache honour it: these images (the first stale lookup
+# refreshes EVERY registered image in one batched ``weight_prep`` launch instead of ~2 cast kernels per
+# weight), the captured graphs (``SynthGraphs._check_weights`` drops them) and every ``weights.DerivedCache``
+# (folded BatchNorm convs, the fused projection weight, the upsampling images, the cast positional table),
+# which rebuilds its value on the next lookup.
+class _Image:
+    """One ``_wcache`` entry: the bf16 ``image`` (layout ``mode``) of ``src`` (a detached view at ``src_ptr`` of
+    ``shape``), current for (``version``, ``gen``) of the parameter that ``owner`` weakly refers to."""
+    __slots__ = ("version", "gen", "owner", "image", "mode", "src_ptr", "shape", "src")
+
+    def __init__(self, owner, image, mode, src):
+        self.version, self.gen, self.owner = owner._version, generation(), weakref.ref(owner)
+        self.image, self.mode = image, mode
+        self.src_ptr, self.shape, self.src = src.data_ptr(), tuple(src.shape), src.detach()
+
+
+_wcache = {}          # (id(param), kind, shape) -> _Image
 _wtable = {"n": -1}   # device descriptor table for the batched refresh
 _wepoch = 0           # bumped whenever the set of cached images changes (fused Adam plan key)
-
-
-def bump_weight_generation():
-    """Mark every cached weight image stale (call after writing parameters through raw pointers)."""
-    global _wgen
-    _wgen += 1
+bump_weight_generation = bump_generation  # the name the optimizer, DDP and style tuning call
 
 
 def _eligible(w: torch.Tensor) -> bool:
@@ -312,8 +321,8 @@ def _refresh_all(device):
     live = []
     for k in list(_wcache):
         e = _wcache[k]
-        owner, w = e[2](), e[7]
-        if owner is None or w.data_ptr() != e[5]:
+        owner, w = e.owner(), e.src
+        if owner is None or w.data_ptr() != e.src_ptr:
             del _wcache[k]
             _wtable["n"] = -1
             _bump_epoch()
@@ -327,7 +336,7 @@ def _refresh_all(device):
         tiles = []
         for i, (e, w, _) in enumerate(live):
             ks = w.shape[2] if w.dim() == 3 else 1
-            desc[i] = (w.data_ptr(), e[3].data_ptr(), w.shape[0], w.shape[1], ks, e[4])
+            desc[i] = (w.data_ptr(), e.image.data_ptr(), w.shape[0], w.shape[1], ks, e.mode)
             cum[i + 1] = cum[i] + w.numel()
             K = w.shape[1] * ks
             for co0 in range(0, w.shape[0], 64):
@@ -347,7 +356,7 @@ def _refresh_all(device):
                                          _stream())
         _check(rc, "ssamd_weight_prep")
     for e, w, owner in live:
-        e[0], e[1] = owner._version, _wgen
+        e.version, e.gen = owner._version, generation()
 
 
 def refresh_stale_images(device):
@@ -355,8 +364,8 @@ def refresh_stale_images(device):
     HIP-graph step reads the images by address and never performs the lookup that refreshes them lazily;
     the fused Adam launch rewrites the arena's images itself, this covers any other writer."""
     for e in _wcache.values():
-        owner = e[2]()
-        if owner is not None and (e[0] != owner._version or e[1] != _wgen):
+        owner = e.owner()
+        if owner is not None and (e.version != owner._version or e.gen != generation()):
             _refresh_all(device)
             return True
     return False
@@ -369,15 +378,14 @@ def _cached(param: torch.Tensor, kind: str, mode: int, make, src: Optional[torch
         return make(src.detach())
     key = (id(param), kind, tuple(src.shape))
     hit = _wcache.get(key)
-    if hit is not None and hit[2]() is param and hit[5] == src.data_ptr() and hit[6] == tuple(src.shape):
-        if hit[0] == param._version and hit[1] == _wgen:
-            return hit[3]
+    if hit is not None and hit.owner() is param and hit.src_ptr == src.data_ptr() and hit.shape == tuple(src.shape):
+        if hit.version == param._version and hit.gen == generation():
+            return hit.image
         if _eligible(src) and has("ssamd_weight_prep"):
             _refresh_all(src.device)
-            return hit[3]
+            return hit.image
     img = make(src.detach())
-    _wcache[key] = [param._version, _wgen, weakref.ref(param), img, mode, src.data_ptr(), tuple(src.shape),
-                    src.detach()]
+    _wcache[key] = _Image(param, img, mode, src)
     _wtable["n"] = -1  # entry set changed: rebuild the descriptor table on the next refresh
     _bump_epoch()
     return img
@@ -826,7 +834,7 @@ class _GroupLinearFn(torch.autograd.Function):
         return (dx, None, None, None, None, *gradslots.split_rows(dw, ws), *gradslots.split_rows(db, bs))
 
 
-_GROUP_CAT = None  # IdCache: first weight of a projection group -> (versions, fused weight, bias)
+_group_cat = DerivedCache()  # first weight of a projection group -> (fused weight, fused bias)
 
 
 def linear_group(x, weights, biases, mailbox=None):
@@ -837,20 +845,11 @@ def linear_group(x, weights, biases, mailbox=None):
             raise ValueError("residual mailbox needs the fused (arena) projection path")
         if torch.is_grad_enabled():
             w, b = torch.cat(weights, 0), torch.cat(biases, 0)
-        else:  # inference outside an arena: the concatenation cached per weight version, held as a Parameter so
-            #     that its bf16 operand image is cached too (_cached); nothing is attached to the model's tensors
-            key = tuple((t.data_ptr(), t._version) for t in weights + biases)
-            global _GROUP_CAT
-            if _GROUP_CAT is None:
-                from . import IdCache
-
-                _GROUP_CAT = IdCache()
-            hit = _GROUP_CAT.get(weights[0])
-            if hit is None or hit[0] != key:
-                wc = torch.nn.Parameter(torch.cat([t.detach() for t in weights], 0), requires_grad=False)
-                hit = (key, wc, torch.cat([t.detach().float() for t in biases], 0).contiguous())
-                _GROUP_CAT.put(weights[0], hit)
-            w, b = hit[1], hit[2]
+        else:  # inference outside an arena: the concatenation cached per version and weight generation, held as a
+            #     Parameter so that its bf16 operand image is cached too (_cached); nothing is attached to the model
+            w, b = _group_cat.get(weights[0], weights + biases, lambda: (
+                torch.nn.Parameter(torch.cat(weights, 0), requires_grad=False),
+                torch.cat([t.float() for t in biases], 0).contiguous()))
         return linear(x, w, b)
     shp = x.shape
     x3 = x.reshape(1, -1, shp[-1]) if x.dim() != 3 else x
@@ -1735,15 +1734,15 @@ def _adam_image_plan(p: torch.Tensor):
     base, n = p.data_ptr(), p.numel()
     weights = {}  # src ptr -> [off, cout, cin, ks, fwd_dst, dgrad_dst, entries]
     for k, e in list(_wcache.items()):
-        owner, w = e[2](), e[7]
-        if owner is None or w.data_ptr() != e[5] or w.device != p.device or not _eligible(w):
+        owner, w = e.owner(), e.src
+        if owner is None or w.data_ptr() != e.src_ptr or w.device != p.device or not _eligible(w):
             continue
         sp = w.data_ptr()
         if not (base <= sp and sp + w.numel() * 4 <= base + n * 4):
             continue
         ks = w.shape[2] if w.dim() == 3 else 1
         rec = weights.setdefault(sp, [(sp - base) // 4, w.shape[0], w.shape[1], ks, 0, 0, []])
-        rec[4 + e[4]] = e[3].data_ptr()
+        rec[4 + e.mode] = e.image.data_ptr()
         rec[6].append(k)
     recs = sorted(weights.values(), key=lambda r: r[0])
     # an element must be updated exactly once: weights whose ranges overlap another image source
@@ -1781,7 +1780,7 @@ def _adam_image_plan(p: torch.Tensor):
         "rcum": torch.from_numpy(rcum).to(dev), "rstart": torch.from_numpy(rstart).to(dev),
         "nr": len(rest), "rtotal": int(rcum[-1]),
         "keys": [k for r in recs for k in r[6]],
-        # the cache entry lists themselves (an entry replaced in _wcache bumps _wepoch -> new plan)
+        # the cache entries themselves (an entry replaced in _wcache bumps _wepoch -> new plan)
         "entries": [_wcache[k] for r in recs for k in r[6]],
     }
     _adam_plan[key] = plan
@@ -1818,11 +1817,11 @@ def clip_adam_step(p, g, m, v, lr, betas, eps, wd, step, clip, norm_out, skipped
 
 def stamp_images(entries):
     """Mark the given cached image entries current (their fused-Adam rewrite is already queued)."""
-    g = _wgen
+    g = generation()
     for e in entries:
-        owner = e[2]()
+        owner = e.owner()
         if owner is not None:
-            e[0], e[1] = owner._version, g
+            e.version, e.gen = owner._version, g
 
 
 # ------------------------------------------------------------------------ multi-tensor copy
@@ -2569,6 +2568,14 @@ class VocPackCap:
 
 
 _TILE_ROWS = {}
+
+
+def set_resblock_tall(v: int):
+    """Select the per-layer ResBlock tile (1 tall: production, 0 regular, 2 half-tall) -- the only way to the
+    library's switch: the kind-3 tile height and the packs' tile tables built from it follow the mode."""
+    lib().ssamd_resblock_set_tall(int(v))
+    _TILE_ROWS.clear()
+    _VOC_PACKS.clear()
 
 
 def voc_tile_rows(kind, C: int, K: int = 0, dil=(0, 0, 0)) -> int:

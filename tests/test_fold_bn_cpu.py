@@ -5,6 +5,7 @@ import torch
 
 def test_gst_folded_eval_matches_unfolded():
     from speakingstyle_amd.config import load_named
+    from speakingstyle_amd.models import layers
     from speakingstyle_amd.models.style import GlobalStyleTokens
 
     pp, mc, _ = load_named("BC2013_GST")
@@ -20,7 +21,7 @@ def test_gst_folded_eval_matches_unfolded():
     ref = m.reference_embedding(mel, lens)  # grad enabled: conv + BatchNorm path
     with torch.no_grad():
         got = m.reference_embedding(mel, lens)  # folded path
-        assert "_fold" in m.__dict__ and m.__dict__["_fold"][1][0][0] == "ref"
+        assert layers._folded.peek(m.convs[0].weight)[0][0] == "ref"  # the folded path ran and was cached
         m.bns[1].running_var.mul_(1.5)  # in place: refolded
         got2 = m.reference_embedding(mel, lens)
     torch.testing.assert_close(got, ref.detach(), rtol=1e-4, atol=1e-5)

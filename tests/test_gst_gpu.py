@@ -163,6 +163,7 @@ def test_gst_eval_folded_matches_cpu():
     """Inference (eval, no grad): the conv + BatchNorm2d stack runs folded (``folded_convs``: ReLU in the GEMM
     epilogue, cached weight images) -- against the fp32 CPU module in eval, with non-trivial running stats."""
     from speakingstyle_amd.config import load_named
+    from speakingstyle_amd.models import layers
     from speakingstyle_amd.models.style import GlobalStyleTokens
 
     pp, mc, _ = load_named("BC2013_GST")
@@ -178,7 +179,7 @@ def test_gst_eval_folded_matches_cpu():
     with torch.no_grad():
         g_c, b_c = cpu(mel.float(), lens)
         g_g, b_g = gpu(mel.to(DEV), lens.to(DEV))
-        assert "_fold" in gpu.__dict__ and gpu.__dict__["_fold"][1][0][0] == "img"
+        assert layers._folded.peek(gpu.convs[0].weight)[0][0] == "img"  # the folded path ran and was cached
         g_g2, _ = gpu(mel.to(DEV), lens.to(DEV))  # cached fold: same result
     assert _rel(g_g, g_c) < 3e-2 and _rel(b_g, b_c) < 3e-2
     assert torch.equal(g_g, g_g2)

@@ -1225,11 +1225,11 @@ def test_resblock_layer_persistent_many_tiles(C, K, d, B, T, tall):
     order -- and vs fp32 torch, with the in-place MRF accumulator."""
     from speakingstyle_amd.models.hifigan import LRELU_SLOPE
 
-    hip.lib().ssamd_resblock_set_tall(tall)
+    hip.set_resblock_tall(tall)
     try:
         _persistent_case(C, K, d, B, T, LRELU_SLOPE)
     finally:
-        hip.lib().ssamd_resblock_set_tall(1)
+        hip.set_resblock_tall(1)
 
 
 def _persistent_case(C, K, d, B, T, LRELU_SLOPE):
@@ -1748,12 +1748,12 @@ def test_fused_adam_images_match_two_kernel_path():
         if images:
             assert len(fresh) > 10  # the model's conv / linear images are covered
             for e in fresh:  # stamped images == fresh casts of the updated weights
-                src = e[7]
+                src = e.src
                 if src.dim() == 2:
-                    want = src.to(torch.bfloat16) if e[4] == 0 else src.t().to(torch.bfloat16)
+                    want = src.to(torch.bfloat16) if e.mode == 0 else src.t().to(torch.bfloat16)
                 else:
-                    want = (src.permute(0, 2, 1) if e[4] == 0 else src.flip(2).permute(1, 2, 0)).to(torch.bfloat16)
-                assert torch.equal(e[3], want.contiguous()), tuple(src.shape)
+                    want = (src.permute(0, 2, 1) if e.mode == 0 else src.flip(2).permute(1, 2, 0)).to(torch.bfloat16)
+                assert torch.equal(e.image, want.contiguous()), tuple(src.shape)
         states.append((opt.arena.data.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone()))
         del m, opt
     for x, y in zip(*states):
