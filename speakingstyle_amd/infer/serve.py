@@ -33,6 +33,7 @@ class Synthesizer:
         self.max_wav = pre["audio"]["max_wav_value"]
         self.lexicon = g2p.load_lexicon(pp["path"]["lexicon_path"], pre["text"].get("language", "en"))
         self._refs = {}  # reference wav path -> (mel [1, T, n_mel], mel_lens [1]) on the device
+        self._prosody = {}  # prosody recording path -> ``transfer.recording_features`` on the device
         self.graphs = None
         if self.device.type == "cuda":
             from .graphs import SynthGraphs
@@ -51,6 +52,15 @@ class Synthesizer:
             hit = self._refs[ref_audio] = (mel, torch.tensor([mel.shape[1]], device=self.device))
         return hit
 
+    def _prosody_features(self, path):
+        hit = self._prosody.get(path)
+        if hit is None:
+            from .transfer import _load_recordings, recording_features
+
+            hit = self._prosody[path] = recording_features(*_load_recordings([path], self.configs[0], self.device),
+                                                            self.configs[0])
+        return hit
+
     def _control(self, text, scalar, per_word):
         if per_word is None:
             return float(scalar)
@@ -60,12 +70,27 @@ class Synthesizer:
     @torch.no_grad()
     def tts(self, text: str, speaker_id: int = 0, ref_audio: Optional[str] = None,
             style_weights: Optional[Sequence[float]] = None, pitch_control: float = 1.0, energy_control: float = 1.0,
-            duration_control: float = 1.0, word_pitch=None, word_energy=None, word_duration=None) -> np.ndarray:
+            duration_control: float = 1.0, word_pitch=None, word_energy=None, word_duration=None,
+            prosody_ref: Optional[str] = None, transfer=("pitch", "energy", "duration"), transfer_strength: float = 1.0,
+            pitch_mode: str = "relative") -> np.ndarray:
         """One utterance -> int16 samples [mel frames * hop].  Style: ``ref_audio`` (a wav path; featurized once
         per path), else GST ``style_weights``, else neutral.  ``word_*``: one factor per word (scaled by the scalar
-        control), as in the single mode."""
+        control), as in the single mode.
+
+        ``prosody_ref`` (a wav path; featurized once per path): say the text the way that recording says it --
+        ``transfer`` names what is taken from it, ``transfer_strength`` in [0, 1] blends it with the model's own
+        prediction, ``pitch_mode`` "relative" keeps the voice's own pitch level (``infer/transfer.py``).  Two eager
+        passes; the captured graphs are neither used nor touched."""
         ctl = [self._control(text, s, w) for s, w in ((pitch_control, word_pitch), (energy_control, word_energy),
                                                       (duration_control, word_duration))]
+        if prosody_ref:
+            from .transfer import synthesize_like
+
+            batch, _, use_ref = single_batch(text, self.configs[0], speaker_id, ref_audio, self.lexicon)
+            out = synthesize_like(self.model, self.configs, batch, vocoder=self.vocoder, controls=ctl, use_ref=use_ref,
+                                  style_weights=style_weights, what=transfer, strength=transfer_strength,
+                                  pitch_mode=pitch_mode, features=self._prosody_features(prosody_ref))
+            return out["wav"][0]
         batch, _, use_ref = single_batch(text, self.configs[0], speaker_id, None, self.lexicon)
         if self.graphs is None:
             if ref_audio:

@@ -425,9 +425,14 @@ class FastSpeech2(nn.Module):
     # ------------------------------------------------------------------ forward
     def forward(self, speakers, texts, src_lens, max_src_len, mels=None, mel_lens=None, max_mel_len=None,
                 p_targets=None, e_targets=None, d_targets=None, p_control=1.0, e_control=1.0, d_control=1.0,
-                style_weights=None, mel_lens_host=None):
+                style_weights=None, mel_lens_host=None, mels_style_only=False):
         """Reference ``model/fastspeech2.py:45-113``.  ``mel_lens_host`` (host int array of the
-        batch's mel lengths, provided by the data pipeline) enables the packed decoder in training."""
+        batch's mel lengths, provided by the data pipeline) enables the packed decoder in training.
+
+        ``mels_style_only`` (synthesis with ``d_targets``, ``infer/transfer.py``): ``mels`` / ``mel_lens`` /
+        ``max_mel_len`` describe the style reference alone.  Without it they are also the teacher-forcing target:
+        the length regulator pads or cuts to ``max_mel_len`` and the decoder runs at ``mel_lens``.  With it the
+        result has ``sum(d_targets)`` frames whatever the reference's length."""
         dev = texts.device
         cd = self.compute_dtype
         if torch.is_grad_enabled() and ops.use_hip(texts):
@@ -453,11 +458,12 @@ class FastSpeech2(nn.Module):
             else:
                 spk = self.speaker_emb(speakers) + self.spker_embed_proj(self.spker_table[speakers])
                 x = ops.add_rowvec(x, spk)
-        training_lr = d_targets is not None
+        training_lr = d_targets is not None and not mels_style_only
         packed = (self.training and training_lr and mel_lens is not None and mel_lens_host is not None
                   and max_mel_len is not None and self.variance_adaptor.packable())
         x, p_pred, e_pred, log_d, d_rounded, mel_lens_out = self.variance_adaptor(
-            x, src_lens, mel_lens, max_mel_len if training_lr else None, p_targets, e_targets, d_targets,
+            x, src_lens, None if mels_style_only else mel_lens, max_mel_len if training_lr else None, p_targets,
+            e_targets, d_targets,
             p_control, e_control, d_control, style, regulate=not packed,
         )
         if packed:
@@ -528,9 +534,15 @@ class FastSpeech2(nn.Module):
 
     @torch.no_grad()
     def infer_front(self, speakers, texts, src_lens, max_src_len, mels=None, mel_lens=None, max_mel_len=None,
-                    p_control=1.0, e_control=1.0, d_control=1.0, style_weights=None, exact_pad=False):
+                    p_control=1.0, e_control=1.0, d_control=1.0, style_weights=None, exact_pad=False, *,
+                    p_targets=None, e_targets=None, d_targets=None, return_preds=False):
         """``infer_packed`` up to the durations (no host sync, fixed shapes: HIP-graph capturable,
         ``infer/graphs.py``) -> (x [B, T, d], rounded durations [B, T], mel_len [B], style).
+
+        ``p_targets`` / ``e_targets`` [B, T] (normalised, phoneme-level): embedded in place of the predictions;
+        ``d_targets`` [B, T] integers: the durations and mel lengths are theirs (0 past ``src_lens``), the duration
+        predictor's output is not used (the second pass of ``infer/transfer.py``).  ``return_preds``: also the
+        pitch / energy predictions [B, T] (controls applied), as a fifth element (p_pred, e_pred).
 
         ``exact_pad``: for the ``pad_for_bucket`` inputs of a capacity run -- each row comes out as its unpadded
         text would (``VarianceAdaptor.forward``); the encoder already masks its pad rows."""
@@ -546,11 +558,16 @@ class FastSpeech2(nn.Module):
             else:
                 spk = self.speaker_emb(speakers) + self.spker_embed_proj(self.spker_table[speakers])
                 x = ops.add_rowvec(x, spk)
-        x, _, _, log_d, _, _ = self.variance_adaptor(x, src_lens, None, None, None, None, None, p_control,
-                                                     e_control, d_control, style, regulate=False,
-                                                     exact_pad=exact_pad)
-        d_rounded, mel_len = ops.duration_round(log_d, src_lens, d_control)
-        return x, d_rounded, mel_len, style
+        x, p_pred, e_pred, log_d, _, _ = self.variance_adaptor(x, src_lens, None, None, p_targets, e_targets, None,
+                                                               p_control, e_control, d_control, style, regulate=False,
+                                                               exact_pad=exact_pad)
+        if d_targets is not None:
+            d_rounded = d_targets.long().clamp(min=0).masked_fill(ops.lengths_to_mask(src_lens, texts.shape[1]), 0)
+            mel_len = d_rounded.sum(1)
+        else:
+            d_rounded, mel_len = ops.duration_round(log_d, src_lens, d_control)
+        front = (x, d_rounded, mel_len, style)
+        return front + ((p_pred, e_pred),) if return_preds else front
 
     @staticmethod
     def pad_text_bucket(T: int) -> int:

@@ -479,3 +479,14 @@ def segment_mean(values, durations):
     if use_hip(values):
         return _hip().segment_mean(values, durations)
     return ref.segment_mean(values, durations)
+
+
+def prosody_transfer(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, energy, pred_pitch, pitch_stats=(0.0, 1.0),
+                     energy_stats=(0.0, 1.0), pitch_mode="relative"):
+    """A recording's prosody as per-token targets: ``dtw``'s path between P syntheses and their recordings, the
+    syntheses' integer durations and the recordings' packed F0 / energy -> (rec_dur [P, Nmax] int32, pitch / energy /
+    voiced [P, Nmax], pitch_ok [P] bool); see ``ops.reference.prosody_transfer``.  On the GPU one workgroup per
+    utterance (``csrc/k_prosody.hip``)."""
+    fn = _hip().prosody_transfer if use_hip(f0) else ref.prosody_transfer
+    return fn(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, energy, pred_pitch, pitch_stats, energy_stats,
+              pitch_mode)

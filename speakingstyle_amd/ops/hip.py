@@ -3275,6 +3275,61 @@ def segment_mean(values, durations):
     return out
 
 
+# ------------------------------------------------------------------------ prosody transfer (csrc/k_prosody.hip)
+_SIGS.update({"ssamd_prosody_transfer": [P, P, I, P, P, P, I, P, P, P, I, F, F, F, F, I, P, P, P, P, P, P, P],
+              "ssamd_prosody_ws_words": [L_]})
+_RESTYPES.update({"ssamd_prosody_ws_words": L_})
+
+
+@torch.no_grad()
+def prosody_transfer(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, energy, pred_pitch, pitch_stats=(0.0, 1.0),
+                     energy_stats=(0.0, 1.0), pitch_mode="relative"):
+    """``ops.reference.prosody_transfer`` on the GPU (fp32): one ``prosody_transfer_kernel`` launch, a workgroup per
+    utterance; three words per recorded frame of the stream's workspace.  ``x_lens`` / ``y_lens`` are host sequences:
+    nothing here waits for the device.  Every utterance comes out bitwise as if alone.
+    -> rec_dur [P, Nmax] int32, pitch / energy / voiced [P, Nmax] fp32, pitch_ok [P] bool."""
+    _, yl = ref.prosody_lens(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, energy, pred_pitch, pitch_stats,
+                             energy_stats, pitch_mode)
+    dev = f0.device
+    path = path.to(torch.int32).contiguous()
+    path_len = path_len.to(torch.int32).contiguous()
+    src_dur = src_dur.to(torch.int32).contiguous()
+    pred_pitch = pred_pitch.detach().float().contiguous()
+    energy = energy.float().contiguous()
+    for t, dt, name in ((path, torch.int32, "path"), (path_len, torch.int32, "path_len"), (src_dur, torch.int32, "src_dur"),
+                        (f0, torch.float32, "f0"), (energy, torch.float32, "energy"),
+                        (pred_pitch, torch.float32, "pred_pitch")):
+        _need(t, dt, "prosody_transfer." + name)
+    npairs, Nmax = src_dur.shape
+    Lmax, Ry = path.shape[1], f0.shape[0]
+    if 3 * Ry >= 2 ** 31 or npairs * max(Lmax, Nmax, 1) >= 2 ** 31:
+        raise ValueError("prosody_transfer: packed frame offsets are 32-bit")
+    rec_dur = torch.empty(npairs, Nmax, device=dev, dtype=torch.int32)
+    pitch = torch.empty(npairs, Nmax, device=dev, dtype=torch.float32)
+    en = torch.empty_like(pitch)
+    voiced = torch.empty_like(pitch)
+    ok = torch.empty(npairs, device=dev, dtype=torch.bool)
+    if npairs == 0 or Nmax == 0:
+        return rec_dur, pitch, en, voiced, ok.fill_(False)
+    import numpy as np
+
+    cu = np.zeros(npairs + 1, dtype=np.int32)
+    cu[1:] = np.cumsum(yl)
+    on_dev = isinstance(src_lens, torch.Tensor) and src_lens.device == dev
+    host = torch.from_numpy(cu if on_dev else np.concatenate([cu, np.asarray(ref._host_lens(src_lens), dtype=np.int32)]))
+    buf = host.pin_memory().to(dev, non_blocking=True)
+    cu_y = buf[:npairs + 1]
+    nl = src_lens.to(torch.int32).contiguous() if on_dev else buf[npairs + 1:]
+    ws = _workspace(dev, int(lib().ssamd_prosody_ws_words(Ry)))
+    rc = lib().ssamd_prosody_transfer(_ptr(path), _ptr(path_len), Lmax, _ptr(src_dur), _ptr(nl), _ptr(pred_pitch), Nmax,
+                                      _ptr(cu_y), _ptr(f0), _ptr(energy), npairs, float(pitch_stats[0]),
+                                      float(pitch_stats[1]), float(energy_stats[0]), float(energy_stats[1]),
+                                      int(pitch_mode == "relative"), _ptr(ws), _ptr(rec_dur), _ptr(pitch), _ptr(en),
+                                      _ptr(voiced), _ptr(ok), _stream())
+    _check(rc, "ssamd_prosody_transfer")
+    return rec_dur, pitch, en, voiced, ok
+
+
 # ------------------------------------------------------------------------ N = 1 heads
 class _HeadFn(torch.autograd.Function):
     """Variance-predictor head Linear(C -> 1) + pad mask (one wave per row)."""

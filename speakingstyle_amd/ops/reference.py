@@ -777,3 +777,149 @@ def pyin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, bins_per_semi
     obs, vp = pyin_obs(cm, sr, tau_min, tau_max, fmin, fmax, bins_per_semitone, no_trough_prob)
     f0 = pyin_decode(obs, vp, frames, sr, hop, fmin, bins_per_semitone, max_transition_rate, switch_prob)
     return (f0, frames, vp, obs) if return_obs else (f0, frames, vp)
+
+
+# --------------------------------------------------------- prosody transfer (csrc/k_prosody.hip semantics)
+PROSODY_MAX_N = 1024  # tokens per utterance the kernel covers (4 per thread of a 256-thread workgroup)
+PROSODY_PITCH_MODES = ("relative", "absolute")
+
+
+def prosody_lens(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, energy, pred_pitch, pitch_stats, energy_stats,
+                 pitch_mode):
+    """Host side of a prosody-transfer batch, validated -> (x_lens, y_lens) as int lists.  ``ValueError`` with the
+    offending value before anything runs."""
+    if pitch_mode not in PROSODY_PITCH_MODES:
+        raise ValueError(f"prosody_transfer: pitch_mode {pitch_mode!r} not supported ({', '.join(PROSODY_PITCH_MODES)})")
+    if path.dim() != 3 or path.shape[2] != 2 or src_dur.dim() != 2 or pred_pitch.shape != src_dur.shape:
+        raise ValueError(f"prosody_transfer: path [P, Lmax, 2] / src_dur, pred_pitch [P, Nmax], got {tuple(path.shape)} / "
+                         f"{tuple(src_dur.shape)} / {tuple(pred_pitch.shape)}")
+    xl, yl = _host_lens(x_lens), _host_lens(y_lens)
+    P, Nmax = src_dur.shape
+    if not (path.shape[0] == path_len.shape[0] == len(xl) == len(yl) == len(src_lens) == P):
+        raise ValueError(f"prosody_transfer: {path.shape[0]} paths / {path_len.shape[0]} path lengths / {len(xl)} x "
+                         f"lengths / {len(yl)} y lengths / {len(src_lens)} token counts for {P} utterances")
+    if Nmax > PROSODY_MAX_N:
+        raise ValueError(f"prosody_transfer: Nmax = {Nmax} exceeds {PROSODY_MAX_N} tokens")
+    for p, (a, b) in enumerate(zip(xl, yl)):
+        if a < 1 or b < 1:
+            raise ValueError(f"prosody_transfer: utterance {p} has lengths ({a}, {b}); an alignment has at least one "
+                             "frame on each side")
+    if f0.dim() != 1 or f0.shape != energy.shape or sum(yl) != f0.shape[0]:
+        raise ValueError(f"prosody_transfer: y lengths sum to {sum(yl)} but f0 / energy are {tuple(f0.shape)} / "
+                         f"{tuple(energy.shape)}")
+    for name, st in (("pitch", pitch_stats), ("energy", energy_stats)):
+        if len(st) != 2 or not float(st[1]) > 0.0:
+            raise ValueError(f"prosody_transfer: {name} statistics must be (mean, std > 0), got {tuple(st)}")
+    return xl, yl
+
+
+def _pad_frames(v, yl):
+    """Packed frames [Ry] -> ([P, Ymax] zero-padded, valid [P, Ymax])."""
+    P, Ymax, dev = len(yl), max(yl), v.device
+    lens = torch.tensor(yl, dtype=torch.long, device=dev)
+    starts = torch.cumsum(lens, 0) - lens
+    j = torch.arange(Ymax, device=dev).unsqueeze(0)
+    valid = j < lens.unsqueeze(1)
+    rows = v[(starts.unsqueeze(1) + j).clamp(max=v.shape[0] - 1)]
+    return torch.where(valid, rows, torch.zeros_like(rows)), valid
+
+
+def prosody_contour(f0, y_lens):
+    """``data.preprocess.interpolate_unvoiced`` of packed F0 tracks [Ry] (Hz, 0 = unvoiced): unvoiced frames take the
+    line between the neighbouring voiced frames, the ends hold the first / last voiced value.
+    -> (g [P, Ymax] zero-padded, valid [P, Ymax], voiced [P, Ymax], ok [P] = the utterance has a voiced frame;
+    without one g is all zero)."""
+    yl = _host_lens(y_lens)
+    f0p, valid = _pad_frames(f0, yl)
+    Ymax, big = f0p.shape[1], f0p.shape[1] + 1
+    v = valid & (f0p > 0)
+    j = torch.arange(Ymax, device=f0.device).unsqueeze(0).expand_as(f0p)
+    a = torch.where(v, j, torch.full_like(j, -1)).cummax(1).values
+    b = torch.where(v, j, torch.full_like(j, big)).flip(1).cummin(1).values.flip(1)
+    has_a, has_b = a >= 0, b < big
+    fa = torch.gather(f0p, 1, a.clamp(min=0))
+    fb = torch.gather(f0p, 1, b.clamp(max=Ymax - 1))
+    line = (fb - fa) / (b - a).clamp(min=1).to(f0.dtype) * (j - a).to(f0.dtype) + fa
+    zero = torch.zeros_like(f0p)
+    g = torch.where(v, f0p, torch.where(has_a & has_b, line, torch.where(has_a, fa, torch.where(has_b, fb, zero))))
+    return torch.where(valid, g, zero), valid, v, v.any(1)
+
+
+@torch.no_grad()
+def prosody_transfer(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, energy, pred_pitch, pitch_stats=(0.0, 1.0),
+                     energy_stats=(0.0, 1.0), pitch_mode="relative", return_contour=False):
+    """A recording's prosody as the per-token targets of the variance adaptor.  ``path`` [P, Lmax, 2] int32 /
+    ``path_len`` [P]: ``dtw``'s alignment of P syntheses (index 0: frame i) with their recordings (index 1: frame j);
+    ``src_dur`` [P, Nmax] the integer token durations of the syntheses, ``src_lens`` [P] their token counts;
+    ``x_lens`` / ``y_lens`` host frame counts; ``f0`` [Ry] (Hz, 0 = unvoiced) / ``energy`` [Ry] the recordings' packed
+    contours; ``pred_pitch`` [P, Nmax] the syntheses' normalised pitch (relative mode only); ``*_stats`` (mean, std)
+    of the normalisation.
+
+      owner(j) = (i_lo + i_hi) >> 1 over the run of path cells of recorded frame j
+      token(j) = #{n : cumsum(src_dur)[n] <= min(owner(j), sum(src_dur) - 1)}: the token whose frames hold owner(j);
+                 frames past the synthesis go to the last token with a duration.  Non-decreasing in j.
+      rec_dur[n] = #{j : token(j) = n}: sums to y_len, 0 where src_dur is 0 (all 0 when every src_dur is)
+      g = ``prosody_contour``; ``pitch_mode="relative"``: g <- g exp(L_pred - L_ref) with L_ref = mean_j ln g[j] and
+          L_pred = the src_dur-weighted mean of ln max(pred_pitch std + mean, 1) -- the recording's contour at the
+          synthesis' own level; ``"absolute"`` and utterances without a voiced frame: g as it is
+      pitch[n] = (mean of g over the token's frames - mean) / std, energy[n] likewise (frames added in increasing j
+          into one accumulator per token), voiced[n] = share of the token's frames with f0 > 0; 0 where rec_dur is 0
+
+    Computes in f0's dtype (float64 = the oracle) on its device.
+    -> rec_dur [P, Nmax] int32, pitch / energy / voiced [P, Nmax], pitch_ok [P] bool[, g [P, Ymax] as used]."""
+    xl, yl = prosody_lens(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, energy, pred_pitch, pitch_stats,
+                          energy_stats, pitch_mode)
+    dev, dt = f0.device, f0.dtype
+    P, Nmax = src_dur.shape
+    Ymax = max(yl) if P else 0
+    if P == 0:
+        z = torch.zeros(0, Nmax, dtype=dt, device=dev)
+        out = (z.to(torch.int32), z, z.clone(), z.clone(), torch.zeros(0, dtype=torch.bool, device=dev))
+        return out + (torch.zeros(0, 0, dtype=dt, device=dev),) if return_contour else out
+    p_mean, p_std = float(pitch_stats[0]), float(pitch_stats[1])
+    e_mean, e_std = float(energy_stats[0]), float(energy_stats[1])
+    nl = _lens_on(src_lens, _host_lens(src_lens), dev)
+    n_idx = torch.arange(Nmax, device=dev).unsqueeze(0)
+    dur = torch.where(n_idx < nl.unsqueeze(1), src_dur.to(dev).long().clamp(min=0), torch.zeros((), dtype=torch.long, device=dev))
+    ends = torch.cumsum(dur, 1)
+    total = ends[:, -1]
+    # runs of equal j: neighbouring cells compared
+    L = path.shape[1]
+    i, j = path[..., 0].long(), path[..., 1].long()
+    ylens = torch.tensor(yl, dtype=torch.long, device=dev)
+    cell = (torch.arange(L, device=dev).unsqueeze(0) < path_len.long().unsqueeze(1)) & (j >= 0) & (j < ylens.unsqueeze(1))
+    jm = torch.where(cell, j, torch.full_like(j, -1))
+    neg = torch.full_like(jm[:, :1], -1)
+    first = cell & (jm != torch.cat([neg, jm[:, :-1]], 1))
+    last = cell & (jm != torch.cat([jm[:, 1:], neg], 1))
+    lo = torch.zeros(P, Ymax + 1, dtype=torch.long, device=dev)
+    hi = torch.zeros(P, Ymax + 1, dtype=torch.long, device=dev)
+    lo.scatter_(1, torch.where(first, j, torch.full_like(j, Ymax)), i)
+    hi.scatter_(1, torch.where(last, j, torch.full_like(j, Ymax)), i)
+    owner = (lo[:, :Ymax] + hi[:, :Ymax]) >> 1
+    key = torch.minimum(owner, (total - 1).unsqueeze(1)).clamp(min=0)
+    tok = torch.searchsorted(ends, key, right=True).clamp(max=Nmax)
+    g, valid, v, ok = prosody_contour(f0, yl)
+    tok = torch.where(valid & (total > 0).unsqueeze(1), tok, torch.full_like(tok, Nmax))  # slot Nmax: no token
+    if pitch_mode == "relative":
+        one = torch.ones_like(g)
+        l_ref = torch.log(torch.where(g > 0, g, one)).sum(1) / ylens.to(dt)
+        hz = (pred_pitch.to(dev, dt) * p_std + p_mean).clamp(min=1.0)
+        l_pred = (dur.to(dt) * torch.log(hz)).sum(1) / total.clamp(min=1).to(dt)
+        scale = torch.where(ok & (total > 0), torch.exp(l_pred - l_ref), torch.ones_like(l_ref))
+        g = g * scale.unsqueeze(1)
+
+    def sums(values):
+        s = torch.zeros(P, Nmax + 1, dtype=dt, device=dev)
+        s.scatter_add_(1, tok, values)
+        return s[:, :Nmax]
+
+    cnt = sums(valid.to(dt))
+    some = cnt > 0
+    c1 = torch.where(some, cnt, torch.ones_like(cnt))
+    zero = torch.zeros_like(cnt)
+    pitch = torch.where(some, (sums(g) / c1 - p_mean) / p_std, zero)
+    en = torch.where(some, (sums(_pad_frames(energy.to(dt), yl)[0]) / c1 - e_mean) / e_std, zero)
+    voiced = torch.where(some, sums(v.to(dt)) / c1, zero)
+    out = (cnt.to(torch.int32), pitch, en, voiced, ok)
+    return out + (g,) if return_contour else out

@@ -10,6 +10,9 @@ prosody control and GST style weights.
   serve:   python synthesize.py --mode serve [--source lines.txt] --restore_step N -p -m -t
            one text per line (from --source or stdin) -> {result_path}/serve_{line:04d}.wav, through the serving
            entry (infer/serve.py: bucketed HIP graphs on the GPU); prints the graph statistics at the end
+  prosody transfer (all modes): --prosody_ref x.wav [--transfer pitch,energy,duration] [--transfer_strength 0..1]
+           [--transfer_pitch relative|absolute]: say the text the way the recording says it (infer/transfer.py);
+           --prosody_ref recording: every utterance's own <raw_path>/<speaker>/<basename>.wav (batch mode)
 """
 import argparse
 import os
@@ -38,6 +41,37 @@ def _choose_vocoder(model_config, choice):
         model_config["vocoder"] = dict(model_config["vocoder"], model="GriffinLim")
 
 
+def _transfer_args(args):
+    """The validated --transfer* flags as ``synthesize_like`` keywords."""
+    from speakingstyle_amd.infer.transfer import check_transfer
+
+    what = check_transfer(args.transfer, args.transfer_strength, args.transfer_pitch)
+    return {"what": what, "strength": args.transfer_strength, "pitch_mode": args.transfer_pitch}
+
+
+def synthesize_with_prosody(model, configs, vocoder, batchs, controls, result_path, args, use_ref, style_weights,
+                            speaker_of=None):
+    """The batches through ``infer.transfer.synthesize_like`` -> ``{result_path}/{basename}.wav``."""
+    from speakingstyle_amd.analysis.objective import _recording
+    from speakingstyle_amd.audio.io import write_wav
+    from speakingstyle_amd.infer.transfer import synthesize_like
+
+    pp = configs[0]
+    kw = _transfer_args(args)
+    for batch in batchs:
+        names = batch[0]
+        if args.prosody_ref == "recording":
+            if speaker_of is None:
+                raise ValueError("--prosody_ref recording needs --mode batch: the recordings are the listed utterances'")
+            recs = [_recording(pp, speaker_of[base], base) for base in names]
+        else:
+            recs = [args.prosody_ref] * len(names)
+        out = synthesize_like(model, configs, batch, recs, vocoder=vocoder, controls=controls, use_ref=use_ref,
+                              style_weights=style_weights, **kw)
+        for wav, name in zip(out["wav"], names):
+            write_wav(os.path.join(result_path, f"{name}.wav"), pp["preprocessing"]["audio"]["sampling_rate"], wav)
+
+
 def serve(args):
     """One wav per input line through ``infer.serve.Synthesizer``."""
     from speakingstyle_amd.audio.io import write_wav
@@ -53,13 +87,20 @@ def serve(args):
             lines = f.read().splitlines()
     else:
         lines = sys.stdin.read().splitlines()
+    extra = {}
+    if args.prosody_ref is not None:
+        if args.prosody_ref == "recording":
+            raise ValueError("--prosody_ref recording needs --mode batch: the recordings are the listed utterances'")
+        kw = _transfer_args(args)
+        extra = {"prosody_ref": args.prosody_ref, "transfer": kw["what"], "transfer_strength": kw["strength"],
+                 "pitch_mode": kw["pitch_mode"]}
     n = 0
     for line in lines:
         if not line.strip():
             continue
         wav = tts.tts(line.strip(), speaker_id=args.speaker_id, ref_audio=args.ref_audio,
                       style_weights=_floats(args.style_weights), pitch_control=args.pitch_control,
-                      energy_control=args.energy_control, duration_control=args.duration_control)
+                      energy_control=args.energy_control, duration_control=args.duration_control, **extra)
         write_wav(os.path.join(result_path, f"serve_{n:04d}.wav"), tts.sampling_rate, wav)
         n += 1
     print(f"wrote {n} wavs to {result_path}; graphs: {tts.stats}")
@@ -88,6 +129,13 @@ def main(argv=None):
     ap.add_argument("--result_path", type=str, default=None)
     ap.add_argument("--vocoder", type=str, choices=["config", "griffin_lim"], default="config",
                     help="config: the model config's vocoder (HiFi-GAN); griffin_lim: no checkpoint needed")
+    ap.add_argument("--prosody_ref", type=str, default=None,
+                    help="a wav whose pitch / energy / timing the synthesis takes over; 'recording': each utterance's "
+                         "own recording under raw_path (batch mode)")
+    ap.add_argument("--transfer", type=str, default="pitch,energy,duration", help="what --prosody_ref transfers")
+    ap.add_argument("--transfer_strength", type=float, default=1.0, help="0 = the model's prediction, 1 = the recording's")
+    ap.add_argument("--transfer_pitch", type=str, choices=["relative", "absolute"], default="relative",
+                    help="relative: the recording's contour at the voice's own level; absolute: its Hz")
     args = ap.parse_args(argv)
     if args.mode == "serve":
         assert args.text is None
@@ -107,8 +155,10 @@ def main(argv=None):
     os.makedirs(result_path, exist_ok=True)
     controls = [args.pitch_control, args.energy_control, args.duration_control]
     use_ref = True
+    speaker_of = None
     if args.mode == "batch":
         ds = TextDataset(args.source, pp, tc)
+        speaker_of = dict(zip(ds.basename, ds.speaker))
         batchs = list(DataLoader(ds, batch_size=args.batch_size, collate_fn=ds.collate_fn))
     else:
         lexicon = g2p.load_lexicon(pp["path"]["lexicon_path"], pp["preprocessing"]["text"].get("language", "en"))
@@ -120,6 +170,10 @@ def main(argv=None):
                 if wv is not None:
                     controls[i] = word_level_controls(groups, _floats(wv), controls[i])
     sw = _floats(args.style_weights)
+    if args.prosody_ref is not None:
+        synthesize_with_prosody(model, configs, vocoder, batchs, controls, result_path, args, use_ref, sw, speaker_of)
+        print("wrote results to", result_path)
+        return
     synthesize(model, configs, vocoder, batchs, controls, result_path, plot=args.plot, use_ref=use_ref,
                style_weights=sw)
     print("wrote results to", result_path)

@@ -4,6 +4,7 @@
 Reports achieved TFLOP/s (GEMM-shaped) or GB/s (memory-bound) per kernel, and
 the hipBLASLt number for the plain-GEMM equivalent (torch.matmul) as a yardstick.
 Usage (GPU box): python tools/bench_kernels.py [--rows 160000] [--iters 20] | --griffin-lim | --dtw | --align | --yin
+       | --pyin | --k256 | --prosody
 """
 import argparse
 import json
@@ -609,6 +610,165 @@ def bench_k256(out_path, rounds=5, iters=20):
         f.write("\n".join(lines) + "\n")
 
 
+def prosody_workload():
+    """The 64 pairs of ``dtw_workloads`` (LJSpeech ``val.txt`` lengths) with what a transfer needs on top, on the CPU:
+    phoneme durations that sum to every x length (the pair's phoneme count, at least one frame each), an F0 track with
+    unvoiced stretches, an energy track and normalised pitch predictions.
+    -> (x, y, x_lens, y_lens, src_dur [64, Nmax] int32, src_lens, f0, energy, pred_pitch)"""
+    import numpy as np
+
+    from speakingstyle_amd.data import synthetic
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    counts = synthetic.ljspeech_phone_counts(os.path.join(root, "preprocessed_data", "LJSpeech", "val.txt"))
+    n = np.random.default_rng(0).choice(counts, size=64)  # the draw of dtw_workloads
+    _, x, y, xl, yl = dtw_workloads()[0]
+    rng = np.random.default_rng(1)
+    n = np.minimum(n, np.asarray(xl))
+    dur = np.zeros((64, int(n.max())), dtype=np.int32)
+    for p in range(64):
+        dur[p, :n[p]] = 1 + rng.multinomial(xl[p] - n[p], np.ones(n[p]) / n[p])
+    ry = sum(yl)
+    f0 = 180.0 + 60.0 * np.sin(np.arange(ry) / 23.0) + rng.normal(0, 5, ry)
+    f0 = np.where(np.convolve(rng.standard_normal(ry + 8), np.ones(9) / 9, "valid") > -0.05, f0, 0.0)
+    return (x, y, xl, yl, torch.from_numpy(dur), torch.from_numpy(n.astype(np.int32)), torch.from_numpy(f0).float(),
+            torch.from_numpy(rng.uniform(1, 60, ry)).float(), torch.from_numpy(rng.standard_normal(dur.shape)).float())
+
+
+def _kernel_resources(src, name):
+    """Register / scratch / LDS figures of kernel ``name`` from a compile of ``src`` for gfx950 (remarks of
+    ``-Rpass-analysis=kernel-resource-usage``)."""
+    import subprocess
+
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-c", os.path.join(csrc, src), "--offload-arch=gfx950",
+           "-std=c++17", "-O3", "-I", csrc, "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull]
+    try:
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    except (OSError, subprocess.TimeoutExpired) as e:
+        return [f"compile figures not available: {e}"]
+    keep, on = [], False
+    for line in r.stdout.splitlines():
+        if "remark:" not in line:
+            continue
+        text = line.split("remark:", 1)[1].split("[-Rpass")[0].strip()
+        if text.startswith("Function Name:"):
+            on = name in text
+        if on and text.split(":")[0] in ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "VGPRs Spill",
+                                         "Occupancy [waves/SIMD]", "LDS Size [bytes/block]"):
+            keep.append(text)
+    return keep or ["compile figures not available: no remarks for " + name]
+
+
+def bench_prosody(out_path, rounds=5):
+    """``ops.prosody_transfer`` (csrc/k_prosody.hip: one launch) against the torch reference of ``ops/reference.py`` on
+    the same GPU tensors, arms alternating in one process, wall time between device synchronisations; the kernel on its
+    own with device events; and ``infer.transfer.synthesize_like`` against the plain packed synthesis of one
+    utterance (LJSpeech model and HiFi-GAN V1 with random weights, ~8 frames per phoneme)."""
+    import time
+
+    from speakingstyle_amd import ops
+    from speakingstyle_amd.ops import reference as ref
+
+    dev = torch.device("cuda")
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    def row(name, arm, v):
+        v = sorted(v)
+        return f"{name:40s} {arm:>28s} {v[len(v) // 2]:10.3f} {v[0]:10.3f} {v[-1]:10.3f}"
+
+    x, y, xl, yl, dur, nl, f0, en, pred = prosody_workload()
+    _, path, plen = ops.dtw(x.to(dev), y.to(dev), xl, yl)
+    a = (path, plen, dur.to(dev), nl.to(dev), xl, yl, f0.to(dev), en.to(dev), pred.to(dev), (180.0, 45.0), (20.0, 12.0),
+         "relative")
+    lines = [f"Prosody transfer, fp32, {torch.cuda.get_device_name(0)}",
+             "prosody_transfer_kernel, compiled for gfx950: " + "; ".join(_kernel_resources("k_prosody.hip",
+                                                                                           "prosody_transfer_kernel")),
+             f"{rounds} alternating rounds per arm after 1 warm-up round; wall time per call between device syncs (ms);",
+             "device-event row: one call of the op, the kernel and the upload of its offset table (3 warm-up calls before each), 20 samples", "",
+             f"{'workload':40s} {'arm':>28s} {'median':>10s} {'min':>10s} {'max':>10s}"]
+    name = "64 utterances, LJSpeech val lengths"
+    t = {"hip ops.prosody_transfer": [], "torch reference": []}
+    for r in range(rounds + 1):
+        for arm, fn in (("hip ops.prosody_transfer", lambda: ops.prosody_transfer(*a)),
+                        ("torch reference", lambda: ref.prosody_transfer(*a))):
+            ms = wall(fn)
+            if r >= 1:
+                t[arm].append(ms)
+    for arm, v in t.items():
+        lines.append(row(name, arm, v))
+    h, q = sorted(t["hip ops.prosody_transfer"]), sorted(t["torch reference"])
+    lines.append(f"{'':40s} {'torch / hip (medians)':>28s} {q[len(q) // 2] / h[len(h) // 2]:10.1f}")
+    lines.append(row(name, "op, device events", [timeit(lambda: ops.prosody_transfer(*a), 1) for _ in range(20)]))
+    got, want = ops.prosody_transfer(*a), ref.prosody_transfer(*a)
+    lines.append(f"{'':40s} frames: {sum(yl)} recorded / {sum(xl)} synthesized, tokens: {int(nl.sum())}; rec_dur equal: "
+                 f"{torch.equal(got[0], want[0])}, largest pitch difference {float((got[1] - want[1]).abs().max()):.2e}")
+
+    # one utterance end to end
+    from speakingstyle_amd.config import load_named
+    from speakingstyle_amd.data.synthetic import SyntheticBatches
+    from speakingstyle_amd.infer.transfer import recording_features, synthesize_like
+    from speakingstyle_amd.models.fastspeech2 import FastSpeech2
+    from speakingstyle_amd.models.hifigan import Generator, default_config
+
+    configs = load_named("LJSpeech")
+    pp, mc = configs[0], configs[1]
+    torch.manual_seed(0)
+    model = FastSpeech2(pp, mc).to(dev)
+    with torch.no_grad():
+        lin = model.variance_adaptor.duration_predictor.linear_layer
+        lin.weight.normal_(0.0, 0.005)
+        lin.bias.fill_(math.log(9.1))
+    model.eval().set_compute_dtype(torch.bfloat16)
+    model.requires_grad_(False)
+    torch.manual_seed(1)
+    voc = Generator(default_config()).eval().fold_weight_norm().to(dev)
+    b = SyntheticBatches(1, device=dev, seed=3, max_seq_len=mc["max_seq_len"]).make_batch()[:9]
+    sr, hop = pp["preprocessing"]["audio"]["sampling_rate"], pp["preprocessing"]["stft"]["hop_length"]
+    ts = torch.arange(int(5.0 * sr), dtype=torch.float64) / sr
+    ph = 2 * math.pi * torch.cumsum(170 + 40 * torch.sin(2 * math.pi * 0.8 * ts), 0) / sr
+    rec = (0.2 * sum(0.6 ** k * torch.sin((k + 1) * ph) for k in range(6)) * (torch.sin(2 * math.pi * 0.5 * ts) > -0.6)
+           + 0.002 * torch.randn(ts.shape[0], dtype=torch.float64)).float().to(dev)
+    stats = {"pitch": (180.0, 45.0), "energy": (20.0, 12.0)}
+    feats = recording_features(rec, [rec.shape[0]], pp)
+    mx = pp["preprocessing"]["audio"]["max_wav_value"]
+
+    def plain():
+        rows, lens, _ = model.infer_packed(*b[2:9])
+        return voc.infer_packed(rows.to(torch.bfloat16), lens, int16_scale=mx).cpu()
+
+    arms = (("plain packed synthesis", plain),
+            ("synthesize_like (features)", lambda: synthesize_like(model, configs, b, vocoder=voc, features=feats,
+                                                                          stats=stats)),
+            ("synthesize_like (samples)", lambda: synthesize_like(model, configs, b, [rec], vocoder=voc,
+                                                                           stats=stats)))
+    t = {k: [] for k, _ in arms}
+    for r in range(rounds + 1):
+        for arm, fn in arms:
+            ms = wall(fn)
+            if r >= 1:
+                t[arm].append(ms)
+    out = synthesize_like(model, configs, b, vocoder=voc, features=feats, stats=stats)
+    name = f"1 utterance, {int(b[4][0])} phonemes"
+    lines += ["", f"{'workload':40s} {'arm':>28s} {'median':>10s} {'min':>10s} {'max':>10s}"]
+    for arm, v in t.items():
+        lines.append(row(name, arm, v))
+    lines.append(f"{'':40s} first pass {out['first_pass']['mel_lens'][0]} frames, recording {feats[3][0]} frames, second "
+                 f"pass {out['mel_lens'][0]} frames")
+    text = "\n".join(lines) + "\n"
+    print(text, end="", flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=160000)
@@ -628,11 +788,16 @@ def main():
                          "kernel-only times, wave_metrics with either tracker (pyin_numerics.txt is written beside --out)")
     ap.add_argument("--k256", action="store_true",
                     help="only the K = 256 Linear GEMMs: tile kernels vs the weight-stationary streaming kernel")
+    ap.add_argument("--prosody", action="store_true",
+                    help="only the prosody-transfer arm: the kernel vs the torch reference on the GPU, and "
+                         "synthesize_like vs plain synthesis for one utterance")
     ap.add_argument("--out", default=None,
                     help="default: profiles/griffin_lim.txt, profiles/dtw.txt, profiles/align.txt, profiles/yin.txt, "
-                         "profiles/pyin.txt, profiles/k256_shapes.txt")
+                         "profiles/pyin.txt, profiles/k256_shapes.txt, profiles/prosody_transfer.txt")
     args = ap.parse_args()
     prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    if args.prosody:
+        return bench_prosody(args.out or os.path.join(prof, "prosody_transfer.txt"))
     if args.k256:
         return bench_k256(args.out or os.path.join(prof, "k256_shapes.txt"), iters=args.iters)
     if args.pyin:
