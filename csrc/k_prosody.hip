@@ -25,53 +25,18 @@
 // L_ref / L_pred: per-thread partial sums in a fixed order, a butterfly inside the wave, the 4 wave sums added in
 // order.  fp32, no atomics, no scratch; an utterance reads nothing but its own rows: bitwise what it is alone.
 #include "common.h"
+#include "wg_scan.h"
 
 namespace {
 
-constexpr int PROS_THREADS = 256;
-constexpr int PROS_WAVES = PROS_THREADS / 64;
+constexpr int PROS_THREADS = WG_SCAN_THREADS;  // block_scan / block_sum (wg_scan.h) are written for this size
+constexpr int PROS_WAVES = WG_SCAN_WAVES;
 constexpr int PROS_MAX_N = 1024;             // tokens per utterance: PROS_PER_THREAD per thread
 constexpr int PROS_PER_THREAD = PROS_MAX_N / PROS_THREADS;
 constexpr int PROS_WS_WORDS = 3;             // workspace words per recorded frame: i_lo, i_hi, g
-constexpr int PROS_NONE = 0x7fffffff;
+constexpr int PROS_NONE = WG_SCAN_NONE;
 constexpr float PROS_LN2 = 0.6931471805599453f;
 constexpr float PROS_LOG2E = 1.4426950408889634f;
-
-struct OpAdd { __device__ __forceinline__ int operator()(int a, int b) const { return a + b; } };
-struct OpMax { __device__ __forceinline__ int operator()(int a, int b) const { return a > b ? a : b; } };
-struct OpMin { __device__ __forceinline__ int operator()(int a, int b) const { return a < b ? a : b; } };
-
-// inclusive scan over the workgroup's threads in thread order; `all` = the value over all of them.  Every thread
-// calls it (two barriers); `wtot` [PROS_WAVES] is free again on return.
-template <class Op>
-__device__ __forceinline__ int block_scan(int v, Op op, int* wtot, int& all) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    if (lane >= d) v = op(o, v);
-  }
-  if (lane == 63) wtot[wave] = v;
-  __syncthreads();
-  all = wtot[0];
-#pragma unroll
-  for (int w = 1; w < PROS_WAVES; ++w) all = op(all, wtot[w]);
-  for (int w = wave - 1; w >= 0; --w) v = op(wtot[w], v);
-  __syncthreads();
-  return v;
-}
-
-// sum over the workgroup in a fixed order, to every thread (two barriers); `ftot` [PROS_WAVES]
-__device__ __forceinline__ float block_sum(float v, float* ftot) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) ftot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = ftot[0];
-#pragma unroll
-  for (int w = 1; w < PROS_WAVES; ++w) s += ftot[w];
-  __syncthreads();
-  return s;
-}
 
 __device__ __forceinline__ float ln_hw(float x) { return __builtin_amdgcn_logf(x) * PROS_LN2; }  // v_log_f32
 

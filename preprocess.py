@@ -18,12 +18,15 @@ def main(argv=None):
     ap.add_argument("-preprocess_config", "--preprocess_config", "-p", dest="pconf", default=None)
     ap.add_argument("-model_config", "--model_config", "-m", dest="mconf", default=None)
     ap.add_argument("--workers", type=int, default=max(1, (os.cpu_count() or 2) // 2))
+    ap.add_argument("--device", choices=("cpu", "cuda"), default=None,
+                    help="batched pipeline with the packed feature ops on this device (pitch extractor pyin | yin); "
+                         "default: the per-utterance host pipeline")
     a = ap.parse_args(argv)
     path = a.pconf or a.config
     if not path:
         ap.error("a preprocess.yaml is required")
     cfg = normalize_preprocess_config(load_yaml(path))
-    return Preprocessor(cfg).build_from_path(workers=a.workers)
+    return Preprocessor(cfg, device=a.device).build_from_path(workers=a.workers)
 
 
 if __name__ == "__main__":

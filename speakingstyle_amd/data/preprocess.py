@@ -22,6 +22,12 @@ joblib+dask, ``preprocessor/bc_2013.py:62-73``).
 transcript through the text frontend (what ``synthesize.py`` feeds the model), the whole utterance's mel is
 stored with frame-level energy and interpolated-F0 contours under ``energy/`` and ``pitch/``, and there is no
 ``duration/``: the model's alignment learner finds the durations in training (``models/aligner.py``).
+
+``Preprocessor(config, device=...)`` (``preprocess.py --device cpu|cuda``) is the batched pipeline: the pool only
+loads (wav, transcript / TextGrid slice), the main process packs about 64 utterances into one vector and runs
+``ops.pyin`` / ``ops.yin``, ``ops.frame_features`` and ``ops.interp_unvoiced`` on it (HIP kernels on ``cuda``, the
+torch references on ``cpu``), and the pitch / energy contours are normalised in memory and written once.  Drop rules,
+statistics and metadata go through the same functions as the per-utterance path.
 """
 from __future__ import annotations
 
@@ -29,6 +35,7 @@ import json
 import os
 import random
 import re
+import time
 from multiprocessing import Pool
 from typing import List, Optional, Tuple
 
@@ -214,7 +221,13 @@ class RunningMoments:
 
 # ------------------------------------------------------------------ Preprocessor
 class Preprocessor:
-    def __init__(self, config, model_config=None):  # second arg accepted for CLI compatibility
+    BATCH_UTTERANCES = 64         # utterances per packed batch of the device pipeline ...
+    BATCH_SAMPLES = 64 * 12 * 22050  # ... and its cap on packed samples (a batch always holds one utterance)
+    DEVICE_EXTRACTORS = ("pyin", "yin")
+
+    def __init__(self, config, model_config=None, device=None):  # second arg accepted for CLI compatibility
+        """``device``: None = the per-utterance host pipeline; "cpu" / "cuda" (or a ``torch.device``) = the batched
+        pipeline with the packed ops on that device."""
         self.config = config
         pp = config["preprocessing"]
         self.in_dir = config["path"]["raw_path"]
@@ -227,6 +240,15 @@ class Preprocessor:
         self.pitch_norm = pp["pitch"]["normalization"]
         self.energy_norm = pp["energy"]["normalization"]
         self.f0_method = pp["pitch"].get("extractor", "dio")
+        self.device = None
+        if device is not None:
+            import torch
+
+            if self.f0_method not in self.DEVICE_EXTRACTORS:
+                raise ValueError(f"preprocessing.pitch.extractor: {self.f0_method!r} has no packed kernel; with a device "
+                                 f"it must be one of {' | '.join(self.DEVICE_EXTRACTORS)}")
+            self.device = torch.device(device)
+        self.timings = {"load": 0.0, "kernels": 0.0, "write": 0.0}  # seconds of the batched pipeline's main process
         self.learned = (pp.get("duration") or {}).get("source", "textgrid") == "learned"
         self.language = pp["text"].get("language", "en")
         self.cleaners = pp["text"]["text_cleaners"]
@@ -303,9 +325,183 @@ class Preprocessor:
             np.save(os.path.join(self.out_dir, kind, f"{speaker}-{kind}-{basename}.npy"), arr)
         return "|".join([basename, speaker, text, raw_text]), remove_outlier(pitch), remove_outlier(energy), mel.shape[1]
 
-    def build_from_path(self, workers: int = 4):
-        for kind in ("mel", "pitch", "energy") + (() if self.learned else ("duration",)):
-            os.makedirs(os.path.join(self.out_dir, kind), exist_ok=True)
+    # ------------------------------------------------------------ batched pipeline (device is not None)
+    def load_utterance(self, speaker: str, basename: str):
+        """The host half of an utterance, as the per-utterance path does it up to the features (runs in the pool and
+        never touches a device): transcript / phones, the wav (resampled; the TextGrid slice [start, end)) and the
+        durations.  -> None (no phones) or (info line, wav float32 [N], durations | None, phones)."""
+        wav_path = os.path.join(self.in_dir, speaker, f"{basename}.wav")
+        lab_path = os.path.join(self.in_dir, speaker, f"{basename}.lab")
+        if self.learned:
+            from ..text import text_to_sequence
+
+            with open(lab_path, encoding="utf-8") as f:
+                raw_text = f.readline().strip("\n")
+            phone = self.transcript_phones(raw_text)
+            text = "{" + " ".join(phone) + "}"
+            n_phone = len(text_to_sequence(text, self.cleaners))
+            if n_phone == 0:
+                return None
+            wav, _ = read_wav(wav_path, self.sampling_rate)
+            return "|".join([basename, speaker, text, raw_text]), wav.astype(np.float32), None, n_phone
+        tg_path = os.path.join(self.out_dir, "TextGrid", speaker, f"{basename}.TextGrid")
+        tiers = parse_textgrid(tg_path)
+        phone, duration, start, end = get_alignment(tiers.get("phones", []), self.sampling_rate, self.hop_length)
+        if start >= end or not phone:
+            return None
+        text = "{" + " ".join(phone) + "}"
+        wav, _ = read_wav(wav_path, self.sampling_rate)
+        wav = wav[int(self.sampling_rate * start): int(self.sampling_rate * end)].astype(np.float32)
+        with open(lab_path, encoding="utf-8") as f:
+            raw_text = f.readline().strip("\n")
+        return "|".join([basename, speaker, text, raw_text]), wav, duration, len(duration)
+
+    def _batch_features(self, batch, window, basis):
+        """One packed batch on the device: a single H2D of the samples, F0 on the unclipped samples, log-mel / energy
+        on the clipped ones, the contours over the frames every utterance keeps, and a single D2H.
+        -> per utterance (mel [T, n_mel], energy [T], f0 [T], contour [T], n_voiced) as host arrays, T = the frames
+        kept (all of them with learned durations, min(frames, sum(durations)) with TextGrids)."""
+        import torch
+
+        from .. import ops
+
+        dev = self.device
+        lens = [len(b[1]) for b in batch]
+        x = torch.from_numpy(np.ascontiguousarray(np.concatenate([b[1] for b in batch]), dtype=np.float32))
+        if dev.type == "cuda":
+            x = x.pin_memory().to(dev, non_blocking=True)
+        if self.f0_method == "pyin":
+            f0, frames, _ = ops.pyin(x, lens, self.sampling_rate, self.hop_length)
+        else:
+            f0, frames = ops.yin(x, lens, self.sampling_rate, self.hop_length)
+        mel, energy, _ = ops.frame_features(x, lens, self.stft.n_fft, self.hop_length, window, basis, 1e-5,
+                                            clip_wave=True)
+        keep = [T if b[2] is None else min(T, sum(b[2])) for b, T in zip(batch, frames)]
+        starts = np.concatenate([[0], np.cumsum(frames)])
+        if keep != frames:  # interpolate_unvoiced sees the truncated contour: its held ends depend on the cut
+            rows = np.concatenate([np.arange(a, a + k) for a, k in zip(starts[:-1], keep)])
+            f0 = f0[torch.from_numpy(rows).to(dev)]
+        contour, n_voiced = ops.interp_unvoiced(f0, keep)
+        n_mel, R, Rk = mel.shape[1], mel.shape[0], f0.shape[0]
+        flat = torch.cat([mel.reshape(-1), energy, f0, contour, n_voiced.to(torch.float32)]).cpu().numpy()
+        mel, energy = flat[:R * n_mel].reshape(R, n_mel), flat[R * n_mel:R * n_mel + R]
+        f0, contour = flat[R * n_mel + R:][:Rk], flat[R * n_mel + R + Rk:][:Rk]
+        n_voiced = flat[R * n_mel + R + 2 * Rk:]
+        out, at = [], 0
+        for a, k, nv in zip(starts[:-1], keep, n_voiced):
+            out.append((mel[a:a + k], energy[a:a + k], f0[at:at + k], contour[at:at + k], int(nv)))
+            at += k
+        return out, frames
+
+    def _finish_utterance(self, item, feats, frames):
+        """The per-utterance rules of ``process_utterance`` / ``process_utterance_unaligned`` on a batch's features:
+        -> None / "short" (dropped) or (info, pitch float64, energy, mel [T, n_mel])."""
+        info, _, duration, n_phone = item
+        mel, energy, f0, contour, n_voiced = feats
+        if self.learned:
+            if mel.shape[0] < n_phone:
+                return "short"
+            if n_voiced <= 1:
+                return None
+            return info, contour.astype(np.float64), energy.copy(), mel
+        T = sum(duration)
+        if frames < T or n_voiced <= 1:
+            return None
+        pitch = f0.astype(np.float64)
+        if self.pitch_phoneme:
+            pitch = phoneme_average(contour.astype(np.float64), duration)
+        energy = phoneme_average(energy, duration) if self.energy_phoneme else energy.copy()
+        return info, pitch, energy, mel
+
+    def _build_batched(self, speakers, jobs, workers: int):
+        import multiprocessing
+
+        dev = self.device
+        window = self.stft.fft_window(dev)
+        basis = self.stft.mel_basis.to(device=dev, dtype=window.dtype).contiguous()
+        shortest = max(self.stft.n_fft, 1024) // 2  # reflect padding of the STFT and of the pitch tracker's frame
+        self.timings = {"load": 0.0, "kernels": 0.0, "write": 0.0}
+        out, held, pm, em = [], [], RunningMoments(), RunningMoments()
+        n_frames = n_short = 0
+
+        def flush(batch):
+            nonlocal n_frames, n_short
+            t0 = time.perf_counter()
+            feats, frames = self._batch_features(batch, window, basis)
+            t1 = time.perf_counter()
+            for item, ft, T in zip(batch, feats, frames):
+                r = self._finish_utterance(item, ft, T)
+                if isinstance(r, str):
+                    n_short += 1
+                if r is None or isinstance(r, str):
+                    continue
+                info, pitch, energy, mel = r
+                basename, speaker = info.split("|")[:2]
+                if not self.learned:
+                    np.save(os.path.join(self.out_dir, "duration", f"{speaker}-duration-{basename}.npy"),
+                            np.asarray(item[2]))
+                np.save(os.path.join(self.out_dir, "mel", f"{speaker}-mel-{basename}.npy"), mel)
+                held.append((f"{speaker}-{{}}-{basename}.npy", pitch, energy))
+                out.append(info)
+                pm.update(remove_outlier(pitch))
+                em.update(remove_outlier(energy))
+                n_frames += mel.shape[0]
+            self.timings["kernels"] += t1 - t0
+            self.timings["write"] += time.perf_counter() - t1
+
+        pool = None
+        if workers > 1:  # fresh processes: the workers only load, and never inherit an open GPU from this one
+            pool = multiprocessing.get_context("spawn").Pool(min(workers, 16), initializer=_init_loader,
+                                                             initargs=(self.config,))
+            items = pool.imap(_load_job, jobs, chunksize=4)
+        else:
+            items = (self.load_utterance(s, b) for s, b in jobs)
+        try:
+            batch, samples = [], 0
+            t0 = time.perf_counter()
+            for (speaker, basename), item in zip(jobs, items):
+                if item is None:
+                    continue
+                if len(item[1]) <= shortest:
+                    raise ValueError(f"{speaker}/{basename}: {len(item[1])} samples; the features need more than "
+                                     f"{shortest}")
+                if batch and (len(batch) >= self.BATCH_UTTERANCES or samples + len(item[1]) > self.BATCH_SAMPLES):
+                    self.timings["load"] += time.perf_counter() - t0
+                    flush(batch)
+                    batch, samples = [], 0
+                    t0 = time.perf_counter()
+                batch.append(item)
+                samples += len(item[1])
+            self.timings["load"] += time.perf_counter() - t0
+            if batch:
+                flush(batch)
+        finally:
+            if pool is not None:
+                pool.terminate()
+                pool.join()
+        if n_short:
+            print(f"Dropped {n_short} utterances with fewer mel frames than phones")
+        t0 = time.perf_counter()
+        p_mean, p_std = (pm.mean, pm.std) if self.pitch_norm else (0.0, 1.0)
+        e_mean, e_std = (em.mean, em.std) if self.energy_norm else (0.0, 1.0)
+        p_min, p_max = self._write_normalized("pitch", [(h[0], h[1]) for h in held], p_mean, p_std)
+        e_min, e_max = self._write_normalized("energy", [(h[0], h[2]) for h in held], e_mean, e_std)
+        self.timings["write"] += time.perf_counter() - t0
+        return self.write_metadata(speakers, out, (p_min, p_max, p_mean, p_std), (e_min, e_max, e_mean, e_std), n_frames)
+
+    def _write_normalized(self, kind, held, mean, std):
+        """``normalize`` on the contours still in memory: each is normalised and written once -> (min, max)."""
+        lo, hi = np.finfo(np.float64).max, np.finfo(np.float64).min
+        for name, v in held:
+            v = self.normalized(v, mean, std)
+            np.save(os.path.join(self.out_dir, kind, name.format(kind)), v)
+            if v.size:
+                lo, hi = min(lo, float(v.min())), max(hi, float(v.max()))
+        return lo, hi
+
+    def list_jobs(self):
+        """-> ({speaker: id}, [(speaker, basename)]) in sorted order: every wav with a transcript (learned durations)
+        or a TextGrid."""
         speakers = {}
         jobs: List[Tuple[str, str]] = []
         for i, spk in enumerate(sorted(os.listdir(self.in_dir))):
@@ -321,6 +517,31 @@ class Preprocessor:
                             jobs.append((spk, base))
                     elif os.path.exists(os.path.join(self.out_dir, "TextGrid", spk, f"{base}.TextGrid")):
                         jobs.append((spk, base))
+        return speakers, jobs
+
+    def write_metadata(self, speakers, out, pitch_stats, energy_stats, n_frames):
+        """``speakers.json``, ``stats.json`` ([min, max, mean, std] each), the 1234-seeded shuffle and ``train.txt`` /
+        ``val.txt``."""
+        with open(os.path.join(self.out_dir, "speakers.json"), "w") as f:
+            json.dump(speakers, f)
+        with open(os.path.join(self.out_dir, "stats.json"), "w") as f:
+            json.dump({"pitch": list(pitch_stats), "energy": list(energy_stats)}, f)
+        random.Random(1234).shuffle(out)
+        val = out[: self.val_size]
+        train = out[self.val_size:]
+        with open(os.path.join(self.out_dir, "train.txt"), "w", encoding="utf-8") as f:
+            f.write("".join(x + "\n" for x in train))
+        with open(os.path.join(self.out_dir, "val.txt"), "w", encoding="utf-8") as f:
+            f.write("".join(x + "\n" for x in val))
+        print("Total time: {:.2f} hours".format(n_frames * self.hop_length / self.sampling_rate / 3600))
+        return out
+
+    def build_from_path(self, workers: int = 4):
+        for kind in ("mel", "pitch", "energy") + (() if self.learned else ("duration",)):
+            os.makedirs(os.path.join(self.out_dir, kind), exist_ok=True)
+        speakers, jobs = self.list_jobs()
+        if self.device is not None:
+            return self._build_batched(speakers, jobs, workers)
         one = self.process_utterance_unaligned if self.learned else self.process_utterance
         if workers > 1:
             with Pool(workers) as pool:
@@ -344,30 +565,35 @@ class Preprocessor:
         e_mean, e_std = (em.mean, em.std) if self.energy_norm else (0.0, 1.0)
         p_min, p_max = self.normalize(os.path.join(self.out_dir, "pitch"), p_mean, p_std)
         e_min, e_max = self.normalize(os.path.join(self.out_dir, "energy"), e_mean, e_std)
-        with open(os.path.join(self.out_dir, "speakers.json"), "w") as f:
-            json.dump(speakers, f)
-        with open(os.path.join(self.out_dir, "stats.json"), "w") as f:
-            json.dump({"pitch": [p_min, p_max, p_mean, p_std], "energy": [e_min, e_max, e_mean, e_std]}, f)
-        random.Random(1234).shuffle(out)
-        val = out[: self.val_size]
-        train = out[self.val_size:]
-        with open(os.path.join(self.out_dir, "train.txt"), "w", encoding="utf-8") as f:
-            f.write("".join(x + "\n" for x in train))
-        with open(os.path.join(self.out_dir, "val.txt"), "w", encoding="utf-8") as f:
-            f.write("".join(x + "\n" for x in val))
-        print("Total time: {:.2f} hours".format(n_frames * self.hop_length / self.sampling_rate / 3600))
-        return out
+        return self.write_metadata(speakers, out, (p_min, p_max, p_mean, p_std), (e_min, e_max, e_mean, e_std), n_frames)
+
+    @staticmethod
+    def normalized(v, mean, std):
+        return (v - mean) / std
 
     @staticmethod
     def normalize(in_dir, mean, std):
         lo, hi = np.finfo(np.float64).max, np.finfo(np.float64).min
         for fn in os.listdir(in_dir):
             p = os.path.join(in_dir, fn)
-            v = (np.load(p) - mean) / std
+            v = Preprocessor.normalized(np.load(p), mean, std)
             np.save(p, v)
             if v.size:
                 lo, hi = min(lo, float(v.min())), max(hi, float(v.max()))
         return lo, hi
+
+
+# ------------------------------------------------------------------ loader pool of the batched pipeline
+_loader = None
+
+
+def _init_loader(config):
+    global _loader
+    _loader = Preprocessor(config)
+
+
+def _load_job(job):
+    return _loader.load_utterance(*job)
 
 
 # ------------------------------------------------------------------ prepare_align

@@ -490,3 +490,21 @@ def prosody_transfer(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, ener
     fn = _hip().prosody_transfer if use_hip(f0) else ref.prosody_transfer
     return fn(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, energy, pred_pitch, pitch_stats, energy_stats,
               pitch_mode)
+
+
+def frame_features(wav, lengths, n_fft, hop, window, basis, clip=1e-5, clip_wave=False):
+    """Log-mel and energy of packed utterances (layout and frame counts of ``yin``; ``window`` the n_fft-point analysis
+    window, ``basis`` [n_mel, n_fft / 2 + 1]; ``clip_wave`` clamps the samples to [-1, 1] in the gather) -> (mel [R,
+    n_mel] row-major per frame row, energy [R], the frame counts as a host list); see
+    ``ops.reference.frame_features``.  On the GPU one workgroup per pair of frame rows, one launch for the batch
+    (``csrc/k_features.hip``)."""
+    fn = _hip().frame_features if use_hip(wav) else ref.frame_features
+    return fn(wav, lengths, n_fft, hop, window, basis, clip, clip_wave)
+
+
+def interp_unvoiced(f0, frames):
+    """The unvoiced (zero) frames of packed F0 contours filled linearly in Hz, ends held (host frame counts
+    ``frames``) -> (contour [R], n_voiced [P] int32); see ``ops.reference.interp_unvoiced``.  On the GPU a workgroup
+    per utterance (``csrc/k_features.hip``)."""
+    fn = _hip().interp_unvoiced if use_hip(f0) else ref.interp_unvoiced
+    return fn(f0, frames)

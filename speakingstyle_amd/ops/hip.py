@@ -3057,6 +3057,73 @@ def yin(wav, lengths, sr, hop, frame=1024, fmin=71.0, fmax=800.0, threshold=0.15
     return (f0, frames, cm) if return_cmnd else (f0, frames)
 
 
+# ------------------------------------------------------------------------ packed feature front-end (csrc/k_features.hip)
+_SIGS.update({"ssamd_frame_features": [P, P, I, I, I, P, P, P, I, F, F, I, P, P, P],
+              "ssamd_interp_unvoiced": [P, P, I, P, P, P]})
+
+_mel_supports = {}  # id(basis) -> (weak reference, version, device int32 [n_mel, 2])
+
+
+def _mel_support(basis):
+    """``ops.reference.mel_support`` of a basis on its device, kept while the tensor lives and is not written to (the
+    table needs the basis on the host: one D2H the first time)."""
+    e = _mel_supports.get(id(basis))
+    if e is not None and e[0]() is basis and e[1] == basis._version:
+        return e[2]
+    if len(_mel_supports) > 64:
+        for k in [k for k, v in _mel_supports.items() if v[0]() is None]:
+            del _mel_supports[k]
+    supp = ref.mel_support(basis).to(basis.device)
+    _mel_supports[id(basis)] = (weakref.ref(basis), basis._version, supp)
+    return supp
+
+
+def frame_features(wav, lengths, n_fft, hop, window, basis, clip=1e-5, clip_wave=False):
+    """``ops.reference.frame_features`` on the GPU (fp32): one ``frame_features_kernel`` launch for the whole
+    mixed-length batch, a workgroup per pair of consecutive frame rows of one utterance; every utterance comes out
+    bitwise as if alone.  ``lengths`` is a host sequence and the pair table one H2D copy: nothing here waits for the
+    device (but the first call with a new basis, which reads it back for the support table)."""
+    lens, frames = ref.feature_plan(wav, lengths, n_fft, hop, window, basis)
+    _need(wav, torch.float32, "frame_features.wav")
+    _need(window, torch.float32, "frame_features.window")
+    _need(basis, torch.float32, "frame_features.basis")
+    dev = wav.device
+    n_mel, R = basis.shape[0], sum(frames)
+    mel = torch.empty(R, n_mel, device=dev, dtype=torch.float32)
+    energy = torch.empty(R, device=dev, dtype=torch.float32)
+    if R == 0:
+        return mel, energy, frames
+    host = ref.frame_pairs(lens, frames)
+    tab = host.pin_memory().to(dev, non_blocking=True)
+    log_clip = float(torch.log(torch.tensor([clip], dtype=torch.float32))[0]) if clip > 0 else float("-inf")
+    rc = lib().ssamd_frame_features(_ptr(wav), _ptr(tab), host.shape[0], int(n_fft), int(hop), _ptr(window), _ptr(basis),
+                                    _ptr(_mel_support(basis)), n_mel, float(clip), log_clip, int(bool(clip_wave)),
+                                    _ptr(mel), _ptr(energy), _stream())
+    _check(rc, "ssamd_frame_features")
+    return mel, energy, frames
+
+
+def interp_unvoiced(f0, frames):
+    """``ops.reference.interp_unvoiced`` on the GPU (fp32): one ``interp_unvoiced_kernel`` launch, a workgroup per
+    utterance; ``frames`` is a host sequence."""
+    import numpy as np
+
+    fr = ref.interp_plan(f0, frames)
+    _need(f0, torch.float32, "interp_unvoiced.f0")
+    dev = f0.device
+    out = torch.empty_like(f0)
+    nv = torch.empty(len(fr), device=dev, dtype=torch.int32)
+    if not fr:
+        return out, nv
+    if f0.shape[0] == 0:
+        return out, nv.zero_()
+    cu = torch.from_numpy(np.concatenate([[0], np.cumsum(fr)]).astype(np.int32))
+    cu = cu.pin_memory().to(dev, non_blocking=True)
+    rc = lib().ssamd_interp_unvoiced(_ptr(f0), _ptr(cu), len(fr), _ptr(out), _ptr(nv), _stream())
+    _check(rc, "ssamd_interp_unvoiced")
+    return out, nv
+
+
 # ------------------------------------------------------------------------ probabilistic YIN (csrc/k_pyin.hip)
 _SIGS.update({"ssamd_pyin_obs": [P, I, I, I, F, F, F, I, F, P, P, P],
               "ssamd_pyin_viterbi": [P, P, P, I, I, I, I, P, F, F, F, F, P, P, P]})

@@ -923,3 +923,131 @@ def prosody_transfer(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, ener
     voiced = torch.where(some, sums(v.to(dt)) / c1, zero)
     out = (cnt.to(torch.int32), pitch, en, voiced, ok)
     return out + (g,) if return_contour else out
+
+
+# --------------------------------------------------------- packed feature front-end (csrc/k_features.hip semantics)
+FEATURE_NFFT = (512, 1024, 2048)
+
+
+def feature_plan(wav, lengths, n_fft, hop, window, basis):
+    """Host side of a packed ``frame_features`` batch, validated -> (sample counts, frame counts 1 + N // hop).
+    ``ValueError`` with the offending value for a transform size the kernel does not cover, a hop <= 0, an utterance
+    too short for the reflect padding (N <= n_fft / 2), lengths that do not add up, or a window / basis of the wrong
+    shape."""
+    n_fft, hop = int(n_fft), int(hop)
+    if n_fft not in FEATURE_NFFT:
+        raise ValueError(f"frame_features: n_fft {n_fft} not covered (512, 1024 or 2048)")
+    if hop <= 0:
+        raise ValueError(f"frame_features: hop {hop} must be positive")
+    if wav.dim() != 1:
+        raise ValueError(f"frame_features: wav must be one packed vector of samples, got shape {tuple(wav.shape)}")
+    if window.dim() != 1 or window.shape[0] != n_fft or basis.dim() != 2 or basis.shape[1] != n_fft // 2 + 1:
+        raise ValueError(f"frame_features: window [n_fft] / basis [n_mel, n_fft / 2 + 1] for n_fft {n_fft}, got "
+                         f"{tuple(window.shape)} / {tuple(basis.shape)}")
+    lens = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    for b, n in enumerate(lens):
+        if n <= n_fft // 2:
+            raise ValueError(f"frame_features: utterance {b} has {n} samples; reflect padding needs more than "
+                             f"n_fft / 2 = {n_fft // 2}")
+        if 2 * n + n_fft >= 2 ** 31:
+            raise ValueError(f"frame_features: utterance {b} has {n} samples; positions inside an utterance are 32-bit")
+    if sum(lens) != wav.shape[0]:
+        raise ValueError(f"frame_features: lengths sum to {sum(lens)} but wav has {wav.shape[0]} samples")
+    frames = [1 + n // hop for n in lens]
+    if sum(frames) >= 2 ** 31 // max(1, basis.shape[0]):
+        raise ValueError(f"frame_features: {sum(frames)} frame rows of {basis.shape[0]} mels; packed offsets are 32-bit")
+    return lens, frames
+
+
+def mel_support(basis):
+    """[first non-zero, last non-zero + 1) of every row of a mel basis -> int32 [n_mel, 2] on the host; (0, 0) for an
+    all-zero row.  Zeros inside the range contribute nothing to the projection, so this is right for any basis."""
+    nz = (basis.detach().cpu() != 0)
+    K = nz.shape[1]
+    any_ = nz.any(1)
+    idx = torch.arange(K)
+    lo = torch.where(nz, idx, torch.full_like(idx, K)).min(1).values
+    hi = torch.where(nz, idx + 1, torch.zeros_like(idx)).max(1).values
+    lo = torch.where(any_, lo, torch.zeros_like(lo))
+    return torch.stack([lo, hi], 1).to(torch.int32)
+
+
+def frame_pairs(lens, frames):
+    """Workgroup table of ``frame_features_kernel``: one entry per pair of consecutive frame rows 2p, 2p + 1 of one
+    utterance (a last odd row stands alone) -> int32 [G, 6] on the host: {sample offset of the utterance, low and high
+    word; N; first frame index inside the utterance; output row; rows in this pair (1 | 2)}."""
+    import numpy as np
+
+    lens, frames = np.asarray(lens, dtype=np.int64), np.asarray(frames, dtype=np.int64)
+    off = np.zeros(len(lens), dtype=np.int64)
+    off[1:] = np.cumsum(lens)[:-1]
+    cu = np.zeros(len(lens), dtype=np.int64)
+    cu[1:] = np.cumsum(frames)[:-1]
+    groups = (frames + 1) // 2
+    u = np.repeat(np.arange(len(lens)), groups)
+    cg = np.zeros(len(lens), dtype=np.int64)
+    cg[1:] = np.cumsum(groups)[:-1]
+    first = 2 * (np.arange(int(groups.sum())) - cg[u])
+    tab = np.stack([off[u] & 0xFFFFFFFF, off[u] >> 32, lens[u], first, cu[u] + first,
+                    np.minimum(2, frames[u] - first)], axis=1)
+    return torch.from_numpy(tab.astype(np.uint32).view(np.int32).reshape(-1, 6))
+
+
+def frame_features(wav, lengths, n_fft, hop, window, basis, clip=1e-5, clip_wave=False):
+    """Log-mel and energy of packed utterances (``wav`` one vector of all samples back to back, host sample counts
+    ``lengths``): per utterance ``torch.stft(center=True, pad_mode="reflect")`` with the n_fft-point ``window`` ->
+    |X| -> log(max(basis @ |X|, clip)) and energy = ||X||_2 over frequency, as ``TacotronSTFT.mel_spectrogram``;
+    ``clip_wave`` clamps the samples to [-1, 1] first.  Computes in wav's dtype (float64 = the oracle) on wav's device.
+    -> (mel [R, n_mel] row-major per frame row, energy [R], the frame counts 1 + N // hop as a host list)."""
+    lens, frames = feature_plan(wav, lengths, n_fft, hop, window, basis)
+    win, fb = window.to(wav.dtype), basis.to(wav.dtype)
+    mels, ens, at = [], [], 0
+    for n in lens:
+        x = wav[at:at + n].unsqueeze(0)
+        at += n
+        if clip_wave:
+            x = x.clamp(-1, 1)
+        mag = torch.stft(x, int(n_fft), int(hop), int(n_fft), window=win, center=True, pad_mode="reflect",
+                         return_complex=True).abs()  # [1, n_fft / 2 + 1, T]
+        mels.append(torch.log(torch.clamp(torch.matmul(fb, mag), min=clip))[0].t())
+        ens.append(torch.norm(mag, dim=1)[0])
+    if not mels:
+        return wav.new_zeros(0, basis.shape[0]), wav.new_zeros(0), frames
+    return torch.cat(mels).contiguous(), torch.cat(ens), frames
+
+
+def interp_plan(f0, frames):
+    """Host frame counts of a packed contour batch, validated -> list[int]."""
+    fr = [int(v) for v in (frames.tolist() if isinstance(frames, torch.Tensor) else frames)]
+    if f0.dim() != 1 or any(t < 0 for t in fr) or sum(fr) != f0.shape[0]:
+        raise ValueError(f"interp_unvoiced: frames sum to {sum(fr)} but f0 has shape {tuple(f0.shape)}")
+    if f0.shape[0] >= 2 ** 31:
+        raise ValueError("interp_unvoiced: packed row counts are 32-bit")
+    return fr
+
+
+def interp_unvoiced(f0, frames):
+    """``data.preprocess.interpolate_unvoiced`` of every utterance of a packed F0 batch (host frame counts
+    ``frames``): the zero frames filled linearly in Hz between the nearest non-zero frames (``np.interp``'s
+    slope * (x - xa) + fa), the ends held; an utterance without a non-zero frame stays as it is.  Computes in f0's
+    dtype.  -> (contour [R], n_voiced [P] int32: the non-zero frames per utterance)."""
+    fr = interp_plan(f0, frames)
+    outs, counts, at = [], [], 0
+    for T in fr:
+        y = f0[at:at + T]
+        at += T
+        v = y != 0
+        nv = int(v.sum())
+        counts.append(nv)
+        if nv == 0 or T == 0:
+            outs.append(y.clone())
+            continue
+        j = torch.arange(T, device=y.device)
+        a = torch.cummax(torch.where(v, j, torch.full_like(j, -1)), 0).values
+        b = torch.flip(torch.cummin(torch.flip(torch.where(v, j, torch.full_like(j, T)), [0]), 0).values, [0])
+        ya, yb = y[a.clamp(min=0)], y[b.clamp(max=T - 1)]
+        mid = (yb - ya) / (b - a).clamp(min=1).to(y.dtype) * (j - a).to(y.dtype) + ya
+        g = torch.where(a < 0, yb, torch.where(b >= T, ya, mid))
+        outs.append(torch.where(v, y, g))
+    out = torch.cat(outs) if outs else f0.new_zeros(0)
+    return out, torch.tensor(counts, dtype=torch.int32, device=f0.device)

@@ -4,7 +4,7 @@
 Reports achieved TFLOP/s (GEMM-shaped) or GB/s (memory-bound) per kernel, and
 the hipBLASLt number for the plain-GEMM equivalent (torch.matmul) as a yardstick.
 Usage (GPU box): python tools/bench_kernels.py [--rows 160000] [--iters 20] | --griffin-lim | --dtw | --align | --yin
-       | --pyin | --k256 | --prosody
+       | --pyin | --k256 | --prosody | --features
 """
 import argparse
 import json
@@ -769,6 +769,206 @@ def bench_prosody(out_path, rounds=5):
             f.write(text)
 
 
+def _median_spread(v):
+    v = sorted(v)
+    return v[len(v) // 2], v[0], v[-1]
+
+
+def bench_features(out_path, rounds=9, iters=20, sr=22050, n_fft=1024, hop=256, n_mel=80):
+    """``ops.frame_features`` (csrc/k_features.hip: one packed launch) on the 64-utterance workload of ``--yin``
+    against (a) the per-utterance loop over ``hip.logmel`` (csrc/k_audio.hip) and (b) ``torch.stft`` + matmul per
+    utterance on the same GPU.  Device events around ``iters`` calls, 3 warm-up calls before each window, the arms
+    interleaved round by round in one process.  The outputs of the three arms are compared at the sizes timed."""
+    from speakingstyle_amd import ops
+    from speakingstyle_amd.audio.stft import TacotronSTFT
+    from speakingstyle_amd.ops import reference as ref
+
+    dev = torch.device("cuda")
+    stft = TacotronSTFT(n_fft, hop, n_fft, n_mel, sr, 0.0, 8000.0)
+    window, basis = stft.fft_window(dev), stft.mel_basis.to(dev).contiguous()
+    name, wav_h, lens = yin_workloads(sr, hop)[0]
+    wav = wav_h.to(dev)
+    offs = [0]
+    for n in lens:
+        offs.append(offs[-1] + n)
+    utts = [wav[a:b].unsqueeze(0) for a, b in zip(offs[:-1], offs[1:])]
+    frames = [1 + n // hop for n in lens]
+    R = sum(frames)
+
+    def packed():
+        return ops.frame_features(wav, lens, n_fft, hop, window, basis)
+
+    def loop():
+        return [hip.logmel(u, n_fft, hop, window, basis) for u in utts]
+
+    def torch_arm():
+        return ref.frame_features(wav, lens, n_fft, hop, window, basis)
+
+    supp = hip._mel_support(basis)
+    tab = ref.frame_pairs(lens, frames).to(dev)
+    mel, energy = torch.empty(R, n_mel, device=dev), torch.empty(R, device=dev)
+    log_clip = float(torch.log(torch.tensor([1e-5]))[0])
+
+    def launch():
+        hip._check(hip.lib().ssamd_frame_features(hip._ptr(wav), hip._ptr(tab), tab.shape[0], n_fft, hop, hip._ptr(window),
+                                                  hip._ptr(basis), hip._ptr(supp), n_mel, 1e-5, log_clip, 0, hip._ptr(mel),
+                                                  hip._ptr(energy), hip._stream()), "ssamd_frame_features")
+
+    arms = (("packed ops.frame_features", packed), ("(a) loop over hip.logmel", loop),
+            ("(b) torch.stft + matmul, same GPU", torch_arm), ("frame_features_kernel alone", launch))
+    t = {a: [] for a, _ in arms}
+    for r in range(rounds):
+        for arm, fn in arms:
+            t[arm].append(timeit(fn, iters))
+    nz = int((basis != 0).sum())
+    lines = [f"Packed log-mel / energy front-end, sr {sr} / n_fft {n_fft} / hop {hop} / {n_mel} mels, fp32, "
+             f"{torch.cuda.get_device_name(0)}",
+             f"workload: {name}: {len(lens)} utterances, {sum(lens)} samples, {R} frame rows "
+             f"({sum((f + 1) // 2 for f in frames)} workgroups of two rows)",
+             f"device events around {iters} calls after 3 warm-up calls; {rounds} rounds, the arms interleaved in one "
+             "process; ms per call", "",
+             f"{'arm':>36s} {'median':>10s} {'min':>10s} {'max':>10s}"]
+    for arm, v in t.items():
+        lines.append(f"{arm:>36s} {'%10.4f %10.4f %10.4f' % _median_spread(v)}")
+    pm, plo, phi = _median_spread(t["packed ops.frame_features"])
+    lm, llo, lhi = _median_spread(t["(a) loop over hip.logmel"])
+    tm = _median_spread(t["(b) torch.stft + matmul, same GPU"])[0]
+    lines += ["", f"(a) / packed: {lm / pm:.2f} at the medians; slowest packed round {phi:.4f} ms against the fastest loop "
+                  f"round {llo:.4f} ms: the packed launch {'beats' if phi < llo else 'does NOT beat'} the loop by more than "
+                  "the spread of the repeats",
+              f"(b) / packed: {tm / pm:.2f} at the medians"]
+    km = _median_spread(t["frame_features_kernel alone"])[0]
+    flop = (R / 2) * (5.0 * n_fft * math.log2(n_fft)) + R * 2.0 * nz
+    lines += [f"kernel alone: {flop / 1e9:.3f} GFLOP (5 n log2 n per complex transform of two rows + 2 per non-zero of "
+              f"the basis, {nz} of {basis.numel()}) -> {flop / (km * 1e-3) / 1e12:.3f} TFLOP/s; it reads "
+              f"{4.0 * sum(lens) / 1e6:.1f} MB of samples once from memory ({n_fft // hop} times through the caches) and "
+              f"writes {4.0 * R * (n_mel + 1) / 1e6:.1f} MB -> {(4.0 * sum(lens) + 4.0 * R * (n_mel + 1)) / (km * 1e-3) / 1e9:.1f}"
+              " GB/s: neither the vector rate nor the memory rate binds; the radix-2 stages go through LDS with a barrier "
+              "each (not measured further: no counter run)"]
+    a, b, c = packed(), loop(), torch_arm()
+    mel_a = torch.cat([m[0].t() for m, _ in b])
+    en_a = torch.cat([e[0] for _, e in b])
+    lines += ["", f"outputs at the sizes timed: max |log-mel packed - loop| {float((a[0] - mel_a).abs().max()):.3e}, "
+                  f"packed - torch {float((a[0] - c[0]).abs().max()):.3e}; max rel energy packed - loop "
+                  f"{float(((a[1] - en_a).abs() / en_a.clamp(min=1e-30)).max()):.3e}, packed - torch "
+                  f"{float(((a[1] - c[1]).abs() / c[1].clamp(min=1e-30)).max()):.3e}"]
+    text = "\n".join(lines) + "\n"
+    print(text, end="", flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
+def write_feature_corpus(root, n_utts=256, sr=22050, seed=0):
+    """A synthetic raw corpus for the end-to-end preprocessing figure: ``n_utts`` int16 wavs with the LJSpeech
+    ``val.txt`` length distribution (the signal of ``yin_workloads``) and a transcript each -> the config
+    (``source: learned``, ``pyin``) without its preprocessed_path."""
+    import numpy as np
+
+    from speakingstyle_amd.audio.io import write_wav
+    from speakingstyle_amd.config import config_dir_triplet, load_yaml, normalize_preprocess_config
+    from speakingstyle_amd.data import synthetic
+
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    counts = synthetic.ljspeech_phone_counts(os.path.join(here, "preprocessed_data", "LJSpeech", "val.txt"))
+    rng = np.random.default_rng(seed)
+    frames = np.clip(np.round(rng.choice(counts, size=n_utts) * 8.1), 100, 1000).astype(np.int64)
+    raw = os.path.join(root, "raw", "LJSpeech")
+    os.makedirs(raw, exist_ok=True)
+    for i, T in enumerate(frames):
+        n = 256 * (int(T) - 1)
+        t = np.arange(n) / sr
+        f0 = 170 + 80 * np.sin(2 * np.pi * 1.1 * t + rng.uniform(0, 6.28))
+        ph = 2 * np.pi * np.cumsum(f0) / sr
+        s = sum(0.6 ** k * np.sin((k + 1) * ph + rng.uniform(0, 6.28)) for k in range(6))
+        voiced = np.sin(2 * np.pi * 0.8 * t + rng.uniform(0, 6.28)) > -0.4
+        x = np.where(voiced, 0.3 * (0.55 + 0.45 * np.sin(2 * np.pi * 3 * t)) * s, 0.0) + 0.01 * rng.standard_normal(n)
+        write_wav(os.path.join(raw, f"S{i:04d}.wav"), sr, (0.5 * x / np.abs(x).max() * 32767).astype(np.int16))
+        with open(os.path.join(raw, f"S{i:04d}.lab"), "w") as f:
+            f.write("printing in the only sense with which we are at present concerned")
+    p = load_yaml(config_dir_triplet("LJSpeech_unaligned")[0])
+    p["path"]["raw_path"] = os.path.join(root, "raw")
+    p["preprocessing"]["val_size"] = 16
+    p["preprocessing"]["pitch"]["extractor"] = "pyin"
+    return normalize_preprocess_config(p), int(frames.sum())
+
+
+def preprocess_host_arm(cfg_path):
+    """The per-utterance host path of ``bench_preprocess`` in a process that never opens the GPU -> one JSON line."""
+    import time
+
+    from speakingstyle_amd.data.preprocess import Preprocessor
+
+    with open(cfg_path) as f:
+        job = json.load(f)
+    t0 = time.perf_counter()
+    out = Preprocessor(job["config"]).build_from_path(workers=job["workers"])
+    print(json.dumps({"seconds": time.perf_counter() - t0, "utterances": len(out)}))
+
+
+def bench_preprocess(out_path, n_utts=256, workers=16):
+    """End to end: ``Preprocessor.build_from_path`` on a synthetic corpus, the per-utterance host path with
+    ``workers`` pool workers against ``device="cuda"`` (``workers`` loaders), wall clock, the two alternating."""
+    import copy
+    import subprocess
+    import tempfile
+    import time
+
+    from speakingstyle_amd.data.preprocess import Preprocessor
+
+    lines = []
+    with tempfile.TemporaryDirectory() as root:
+        config, total = write_feature_corpus(root, n_utts)
+        runs = {"host": [], "cuda": []}
+        split = []
+        for r in range(2):
+            for arm in ("cuda", "host")[:2 - r]:  # the host path takes minutes: one run of it
+                cfg = copy.deepcopy(config)
+                cfg["path"]["preprocessed_path"] = os.path.join(root, f"pre_{arm}_{r}")
+                if arm == "host":  # its forked workers must not inherit this process's open GPU: a process of its own
+                    cfg_path = os.path.join(root, f"host_{r}.json")
+                    with open(cfg_path, "w") as f:
+                        json.dump({"config": cfg, "workers": workers}, f)
+                    res = subprocess.run([sys.executable, os.path.abspath(__file__), "--preprocess-host-arm", cfg_path],
+                                         check=True, stdout=subprocess.PIPE, text=True)
+                    got = json.loads(res.stdout.strip().split("\n")[-1])
+                    runs[arm].append(got["seconds"])
+                    assert got["utterances"] == n_utts, got
+                    continue
+                pre = Preprocessor(cfg, device="cuda")
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = pre.build_from_path(workers=workers)
+                torch.cuda.synchronize()
+                runs[arm].append(time.perf_counter() - t0)
+                assert len(out) == n_utts, (arm, len(out))
+                split.append(dict(pre.timings))
+    sec = total * 256 / 22050
+    lines += [f"Preprocessor.build_from_path end to end, {torch.cuda.get_device_name(0)}: {n_utts} synthetic utterances "
+              f"({total} frames, {sec / 60:.1f} min of audio at 22050 Hz, LJSpeech val.txt lengths), source: learned, "
+              f"extractor: pyin, {workers} pool workers in either arm; wall clock of the whole call, three "
+              "runs (cuda, host, cuda; the first cuda run also loads the kernel library; every run starts its pool)", "",
+              f"{'arm':>28s} {'run 1 (s)':>10s} {'run 2 (s)':>10s}"]
+    lines.append(f"{'per-utterance host path':>28s} {runs['host'][0]:10.2f} {'-':>10s}")
+    lines.append(f"{'device=cuda':>28s} {runs['cuda'][0]:10.2f} {runs['cuda'][1]:10.2f}")
+    lines += ["", f"host / cuda: {runs['host'][0] / runs['cuda'][0]:.2f} against the first cuda run, "
+                  f"{runs['host'][0] / runs['cuda'][1]:.2f} against the second",
+              "", "main-process split of the cuda runs (s): load = waiting for the loader pool (process start, wav "
+              "decoding, text frontend), kernels = H2D + pyin + frame_features + interp_unvoiced + the D2H that ends the "
+              "batch, write = per-utterance rules, statistics and .npy files"]
+    for r, s in enumerate(split, 1):
+        lines.append(f"  run {r}: load {s['load']:.2f}  kernels {s['kernels']:.2f}  write {s['write']:.2f}")
+    bound = max(split[-1], key=split[-1].get)
+    lines.append(f"the second cuda run is bound by: {bound}")
+    text = "\n".join(lines) + "\n"
+    print(text, end="", flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=160000)
@@ -791,11 +991,22 @@ def main():
     ap.add_argument("--prosody", action="store_true",
                     help="only the prosody-transfer arm: the kernel vs the torch reference on the GPU, and "
                          "synthesize_like vs plain synthesis for one utterance")
+    ap.add_argument("--features", action="store_true",
+                    help="only the feature front-end: the packed ops.frame_features launch vs the per-utterance loop over "
+                         "hip.logmel and torch.stft + matmul (profiles/features.txt), then Preprocessor end to end, host "
+                         "path vs device=\"cuda\" (profiles/preprocess_gpu.txt beside --out)")
+    ap.add_argument("--preprocess-host-arm", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--out", default=None,
                     help="default: profiles/griffin_lim.txt, profiles/dtw.txt, profiles/align.txt, profiles/yin.txt, "
                          "profiles/pyin.txt, profiles/k256_shapes.txt, profiles/prosody_transfer.txt")
     args = ap.parse_args()
     prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    if args.preprocess_host_arm:
+        return preprocess_host_arm(args.preprocess_host_arm)
+    if args.features:
+        out = args.out or os.path.join(prof, "features.txt")
+        bench_features(out)
+        return bench_preprocess(os.path.join(os.path.dirname(os.path.abspath(out)), "preprocess_gpu.txt"))
     if args.prosody:
         return bench_prosody(args.out or os.path.join(prof, "prosody_transfer.txt"))
     if args.k256:
