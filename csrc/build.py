@@ -116,52 +116,37 @@ def build_sanitized(verbose=False):
     return exes
 
 
-def build_blockmap_selftest():
-    """The attention block map (csrc/attn_blockmap.h) as plain host code under ASan+UBSan: returns the
-    self-test executable (csrc/selftest_attn_blockmap.cpp) in build/sanitize/."""
+def build_selftest(name, headers):
+    """A plain-C++ header shared by kernels and host (csrc/<header>) as host code under ASan+UBSan: returns the
+    self-test executable (csrc/selftest_<name>.cpp) in build/sanitize/."""
     out_dir = os.path.join(ROOT, "build", "sanitize")
     os.makedirs(out_dir, exist_ok=True)
-    test = os.path.join(HERE, "selftest_attn_blockmap.cpp")
-    exe = os.path.join(out_dir, "selftest_attn_blockmap")
-    if _stale(exe, [test, os.path.join(HERE, "attn_blockmap.h")]):
+    test = os.path.join(HERE, f"selftest_{name}.cpp")
+    exe = os.path.join(out_dir, f"selftest_{name}")
+    if _stale(exe, [test] + [os.path.join(HERE, h) for h in headers]):
         _run(["g++", "-O1", "-g", "-std=c++17", "-I", HERE] + SANITIZERS["asan"] + ["-o", exe, test])
     return exe
+
+
+# name -> the headers its self-test covers (tests/test_*_host.py)
+SELFTESTS = {"attn_blockmap": ["attn_blockmap.h"], "gl_frames": ["gl_frames.h"], "dtw_index": ["dtw_index.h"],
+             "k256_split": ["k256_split.h"], "gemm_route": ["gemm_route.h", "k256_split.h"]}
+
+
+def build_blockmap_selftest():
+    return build_selftest("attn_blockmap", SELFTESTS["attn_blockmap"])
 
 
 def build_gl_selftest():
-    """The Griffin-Lim index arithmetic (csrc/gl_frames.h) as plain host code under ASan+UBSan: returns the
-    self-test executable (csrc/selftest_gl_frames.cpp) in build/sanitize/."""
-    out_dir = os.path.join(ROOT, "build", "sanitize")
-    os.makedirs(out_dir, exist_ok=True)
-    test = os.path.join(HERE, "selftest_gl_frames.cpp")
-    exe = os.path.join(out_dir, "selftest_gl_frames")
-    if _stale(exe, [test, os.path.join(HERE, "gl_frames.h")]):
-        _run(["g++", "-O1", "-g", "-std=c++17", "-I", HERE] + SANITIZERS["asan"] + ["-o", exe, test])
-    return exe
+    return build_selftest("gl_frames", SELFTESTS["gl_frames"])
 
 
 def build_dtw_selftest():
-    """The DTW direction-plane index arithmetic (csrc/dtw_index.h) as plain host code under ASan+UBSan: returns the
-    self-test executable (csrc/selftest_dtw_index.cpp) in build/sanitize/."""
-    out_dir = os.path.join(ROOT, "build", "sanitize")
-    os.makedirs(out_dir, exist_ok=True)
-    test = os.path.join(HERE, "selftest_dtw_index.cpp")
-    exe = os.path.join(out_dir, "selftest_dtw_index")
-    if _stale(exe, [test, os.path.join(HERE, "dtw_index.h")]):
-        _run(["g++", "-O1", "-g", "-std=c++17", "-I", HERE] + SANITIZERS["asan"] + ["-o", exe, test])
-    return exe
+    return build_selftest("dtw_index", SELFTESTS["dtw_index"])
 
 
 def build_k256_selftest():
-    """The K = 256 GEMM work split (csrc/k256_split.h) as plain host code under ASan+UBSan: returns the
-    self-test executable (csrc/selftest_k256_split.cpp) in build/sanitize/."""
-    out_dir = os.path.join(ROOT, "build", "sanitize")
-    os.makedirs(out_dir, exist_ok=True)
-    test = os.path.join(HERE, "selftest_k256_split.cpp")
-    exe = os.path.join(out_dir, "selftest_k256_split")
-    if _stale(exe, [test, os.path.join(HERE, "k256_split.h")]):
-        _run(["g++", "-O1", "-g", "-std=c++17", "-I", HERE] + SANITIZERS["asan"] + ["-o", exe, test])
-    return exe
+    return build_selftest("k256_split", SELFTESTS["k256_split"])
 
 
 if __name__ == "__main__":

@@ -23,7 +23,8 @@
 // that share an A panel run on one XCD's L2.
 #include <mutex>
 #include "common.h"
-#include "k256_split.h"
+#include "gemm_route.h"
+#include <utility>
 #include <type_traits>
 
 namespace {
@@ -2489,7 +2490,7 @@ __global__ void __launch_bounds__(NT, 2) conv_wgrad_reg_kernel(const bf16_t* __r
       }
 }
 
-// Skinny-M implicit-GEMM conv (M <= g_skinny_maxm = 1024 rows: a batch-1 utterance's phonemes and frames, the first
+// Skinny-M implicit-GEMM conv (M <= skinny_maxm = 1024 rows: a batch-1 utterance's phonemes and frames, the first
 // vocoder stages, per-utterance style vectors): the tile machinery above pays a 256-row prologue / epilogue for a
 // handful of rows and leaves most CUs idle.  Here a block of NWV waves owns a 16-row x 16-column output tile and
 // splits the k-steps (32 deep) over its waves, operands straight from global memory in the MFMA fragment layout
@@ -2767,27 +2768,75 @@ __global__ void __launch_bounds__(256) colsum_kernel(const bf16_t* __restrict__ 
 
 }  // namespace
 
-static bool g_force_lds_epilogue = false;
-static int g_gemm_variant = -1;  // -1 auto, 0: register staging, 1: LDS-DMA 128x128, 2: LDS-DMA 3-stage ring 256x128
-// s_setprio 1 for waves 4-7 of the 8-wave big64 blocks (MI355X_MICROARCH "static priority for the
-// younger half"), measured per kernel (tools/exp_prio.py): weight gradients on packed rows -2..-4 %,
-// others neutral -> on for wgrad; forward mixed (k9 N = 1024 fwd -4 %, k9 N = 256 dgrad +8 %) -> on for
-// N >= 1024 convs only
-static int g_gemm_prio = -1, g_wgrad_prio = 1;  // forward -1: auto (on for wide k > 1 convs only)
-SSAMD_API void ssamd_gemm_set_prio(int v) { g_gemm_prio = v; }
-static int g_gemm_ngrp = 1;  // 256x256 tile order: N-tile groups (tile_of); experiment knob
-SSAMD_API void ssamd_gemm_set_ngrp(int v) { g_gemm_ngrp = v; }
-SSAMD_API void ssamd_wgrad_set_prio(int v) { g_wgrad_prio = v; }
-static int g_splitk = -1;        // -1 auto, 0 off, S > 1 forced slices (big64 split-K + reduce)
-static int g_ring_maxk = 0, g_ring_maxn = 256;  // 0: the 256x128 ring only for <= 64 big tiles (A/B knob)
-static int g_splitk_tiny = 3;    // min k-steps per slice for <= 8 tiles (0: the general rule only)
-static int g_skinny = 1;         // skinny_gemm_kernel for M <= g_skinny_maxm rows (0: off, A/B)
-// 8-wave skinny blocks from this many k-steps (0: always 4 waves).  Batch 1: 4 waves 1.674 / 1.676 ms, 8 from 16
-// steps 1.625 / 1.624 / 1.605, from 8 steps 1.613 / 1.618; 16 waves from 32 or 64 steps no better (r6_b1_latency.txt)
-static int g_skinny_w8 = 16;
-static int g_skinny_maxm = 1024;
-static int g_skinny_any_cin = 1;  // the skinny kernel also for Cin % 32 != 0 (per-lane taps; 0: tile kernels, A/B)  // measured at batch 1: 64 -> 2.19 ms, 128 -> 1.80, 1024 -> 1.76 (r6_b1_latency.txt)
-static int g_num_cus_gemm = 256;
+// The route functions (gemm_route.h) decide with these sizes; the kernels above are built with them
+static_assert(rk::BM == BM && rk::BN == BN && rk::BK == BK && rk::NT == NT && rk::BM3 == BM3 && rk::BG == BG &&
+              rk::NT3 == NT3 && rk::LDS_EPI == BM * CSTRIDE * 4 && rk::RING_LDS == NSTAGE * STAGE_BYTES &&
+              rk::B64_LDS == B64_LDS && rk::K2_LDS == K2_LDS && rk::WB64_LDS >= 2 * WB64_STAGE &&
+              rk::W128_LDS == 2 * 2 * RB * 256 && rk::ACT_RELU == ACT_RELU && rk::ACT_LRELU == ACT_LRELU &&
+              rk::EPI_GEN == EPI_GEN && rk::EPI_BNH == EPI_BNH && rk::EPI_MASK == EPI_MASK, "gemm_route.h");
+
+static GemmKnobs g_knobs;  // every dispatch switch; each setter writes its field
+SSAMD_API void ssamd_gemm_set_prio(int v) { g_knobs.prio = v; }
+SSAMD_API void ssamd_gemm_set_ngrp(int v) { g_knobs.ngrp = v; }
+SSAMD_API void ssamd_gemm_set_splitk(int v) { g_knobs.splitk = v; }
+SSAMD_API void ssamd_gemm_set_splitk_tiny(int v) { g_knobs.splitk_tiny = v; }
+SSAMD_API void ssamd_gemm_set_ring_maxk(int v) { g_knobs.ring_maxk = v; }
+SSAMD_API void ssamd_gemm_set_ring_maxn(int v) { g_knobs.ring_maxn = v; }
+SSAMD_API void ssamd_gemm_set_skinny(int v) { g_knobs.skinny = v; }
+SSAMD_API void ssamd_gemm_set_skinny_maxm(int v) { g_knobs.skinny_maxm = v; }
+SSAMD_API void ssamd_gemm_set_skinny_w8(int v) { g_knobs.skinny_w8 = v; }
+SSAMD_API void ssamd_gemm_set_skinny_any_cin(int v) { g_knobs.skinny_any_cin = v; }
+SSAMD_API void ssamd_gemm_set_epilogue(int lds_staged) { g_knobs.force_lds_epilogue = lds_staged != 0; }
+SSAMD_API void ssamd_gemm_set_variant(int v) { g_knobs.variant = v; }
+SSAMD_API void ssamd_gemm_set_buf(int v) { g_knobs.buf = v; }
+SSAMD_API void ssamd_gemm_set_stg(int v) { g_knobs.stg = v; }
+SSAMD_API void ssamd_gemm_set_mask_pre(int v) { g_knobs.mask_pre = v; }
+SSAMD_API void ssamd_gemm_set_bnh_stg(int v) { g_knobs.bnh_stg = v; }
+SSAMD_API void ssamd_gemm_set_k256(int v) { g_knobs.k256 = v; }
+SSAMD_API void ssamd_gemm_set_k256_blocks(int v) { g_knobs.k256_blocks = v; }
+SSAMD_API void ssamd_wgrad_set_prio(int v) { g_knobs.wgrad_prio = v; }
+SSAMD_API void ssamd_wgrad_set_imm(int v) { g_knobs.wgrad_imm = v; }
+SSAMD_API void ssamd_wgrad_set_buf(int v) { g_knobs.wgrad_buf = v; }
+SSAMD_API void ssamd_wgrad_set_pp(int v) { g_knobs.wgrad_pp = v; }
+SSAMD_API void ssamd_wgrad_set_blocks(int b) { g_knobs.wgrad_blocks = b > 0 ? b : 0; }
+SSAMD_API void ssamd_wgrad_set_variant(int v) { g_knobs.wgrad_variant = v; }
+static hipStream_t g_wgrad_cus_stream = nullptr;  // the stream wgrad_cus applies to ((hipStream_t)-1: every stream)
+SSAMD_API void ssamd_wgrad_set_cus(hipStream_t s, int n) {
+  g_knobs.wgrad_cus = n > 0 ? n : 0;
+  g_wgrad_cus_stream = s;
+}
+
+static int g_cus_dev[64];
+static int device_cus() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (!g_cus_dev[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    g_cus_dev[dev] = n;
+  }
+  return g_cus_dev[dev];
+}
+
+// One kernel family: at(integral_constant<int, i>) names the instantiation for tab[i] (gemm_route.h) -- the only
+// place it is named -- and the family's first use allows all of them `lds` bytes of dynamic LDS.  Flags that are
+// not in the table have no kernel: nullptr, which the launchers turn into -5.
+template <class Fn, class F, int N, class At, int... I>
+static Fn family_kernel(const F (&tab)[N], const F& want, int lds, At at, std::integer_sequence<int, I...>) {
+  static const Fn fns[N] = {at(std::integral_constant<int, I>{})...};
+  static const bool ready = [lds] {
+    for (Fn f : fns) allow_lds(f, lds);
+    return true;
+  }();
+  (void)ready;
+  const int i = flags_index(tab, want);
+  return i < 0 ? nullptr : fns[i];
+}
+template <class Fn, class F, int N, class At>
+static Fn family_kernel(const F (&tab)[N], const F& want, int lds, At at) {
+  return family_kernel<Fn>(tab, want, lds, at, std::make_integer_sequence<int, N>{});
+}
+
 // Split-K fp32 partials: one workspace per (device, stream).  A process-global buffer would hand a
 // foreign-device pointer to a second GPU and let GEMMs on two streams race on the same partials.
 struct SplitKWs { int dev; hipStream_t s; void* p; size_t bytes; };
@@ -2830,41 +2879,6 @@ static void* splitk_workspace(hipStream_t s, size_t need) {
   }
   return e->p;
 }
-SSAMD_API void ssamd_gemm_set_splitk(int v) { g_splitk = v; }
-SSAMD_API void ssamd_gemm_set_splitk_tiny(int v) { g_splitk_tiny = v; }
-SSAMD_API void ssamd_gemm_set_ring_maxk(int v) { g_ring_maxk = v; }
-SSAMD_API void ssamd_gemm_set_skinny(int v) { g_skinny = v; }
-SSAMD_API void ssamd_gemm_set_skinny_maxm(int v) { g_skinny_maxm = v; }
-SSAMD_API void ssamd_gemm_set_skinny_w8(int v) { g_skinny_w8 = v; }
-SSAMD_API void ssamd_gemm_set_skinny_any_cin(int v) { g_skinny_any_cin = v; }
-SSAMD_API void ssamd_gemm_set_ring_maxn(int v) { g_ring_maxn = v; }
-
-SSAMD_API void ssamd_gemm_set_epilogue(int lds_staged) { g_force_lds_epilogue = lds_staged != 0; }
-SSAMD_API void ssamd_gemm_set_variant(int v) { g_gemm_variant = v; }
-
-static int g_gemm_buf = 1;  // big64 (FASTK) LDS-DMA through buffer descriptors (0: flat global_load_lds)
-SSAMD_API void ssamd_gemm_set_buf(int v) { g_gemm_buf = v; }
-// big64 buffer-descriptor path: 1 = the staggered 8-phase main loop for K >= 512 (tools/exp_stg.py: +5 % on
-// the k9 convs and K = 1024, +2 % PostNet k5, -1..4 % at K = 256 where the prologue / epilogue dominate)
-static int g_gemm_stg = 1;
-static int g_gemm_mask_pre = 1;  // EPI_MASK for the ReLU-mask data gradient (0: the generic epilogue, A/B)
-static int g_gemm_bnh_stg = 1;   // the BatchNorm-backward-head data gradient on the staggered main loop (0: A/B)
-SSAMD_API void ssamd_gemm_set_bnh_stg(int v) { g_gemm_bnh_stg = v; }
-SSAMD_API void ssamd_gemm_set_mask_pre(int v) { g_gemm_mask_pre = v; }
-SSAMD_API void ssamd_gemm_set_stg(int v) { g_gemm_stg = v; }
-// weight-stationary K = 256 kernel (conv_gemm_k256_kernel): -1 auto (the measured rule in conv_gemm_impl), 0 off,
-// 1 on wherever the shape qualifies regardless of M
-static int g_gemm_k256 = -1;
-static int g_k256_min_rows = 28672;  // N = 512 / 768: the measured crossover lies between 14336 and 28672 rows
-static int g_k256_blocks = 0;  // > 0: grid budget instead of the device's CUs (tests: many chunks per block)
-SSAMD_API void ssamd_gemm_set_k256(int v) { g_gemm_k256 = v; }
-SSAMD_API void ssamd_gemm_set_k256_blocks(int v) { g_k256_blocks = v; }
-static int device_cus();
-
-// every byte offset of the descriptors must stay below the out-of-range marker 0x80000000
-static bool big64_buf_ok(const ConvGeom& g) {
-  return g_gemm_buf != 0 && (long)(g.M + g.pad) * g.Cin * 2 < (1L << 31) && (long)g.N * g.K * 2 + 512 < (1L << 31);
-}
 
 static ConvGeom make_geom(int B, int L, int Cin, int ks, int dil, int pad, int N) {
   ConvGeom g;
@@ -2874,306 +2888,111 @@ static ConvGeom make_geom(int B, int L, int Cin, int ks, int dil, int pad, int N
   g.cu = nullptr;
   g.nseq = 0;
   g.ksplit = 0;
-  g.prio = g_gemm_prio < 0 ? (N >= 1024 && ks > 1) : g_gemm_prio;
+  g.prio = g_knobs.prio < 0 ? (N >= 1024 && ks > 1) : g_knobs.prio;
   const int nN = (N + 255) / 256;
-  g.ngrp = (g_gemm_ngrp > 1 && nN % g_gemm_ngrp == 0) ? g_gemm_ngrp : 1;
+  g.ngrp = (g_knobs.ngrp > 1 && nN % g_knobs.ngrp == 0) ? g_knobs.ngrp : 1;
   return g;
 }
 
+using TileFn = void (*)(const bf16_t*, const bf16_t*, const float*, const bf16_t*, const bf16_t*, const int64_t*, void*,
+                        ConvGeom, int, int, EpiX);  // big64, ring
+using C128Fn = void (*)(const bf16_t*, const bf16_t*, const float*, const bf16_t*, const bf16_t*, const int64_t*, void*,
+                        ConvGeom, int, int);
+using SkinnyFn = void (*)(const bf16_t*, const bf16_t*, const float*, const bf16_t*, const bf16_t*, const int64_t*,
+                          void*, int, ConvGeom, int, int, EpiX);
+using K256Fn = void (*)(const bf16_t*, const bf16_t*, const float*, const unsigned char*, bf16_t*, int, int, int);
+
+static TileFn big64_kernel(const GemmFlags& fl) {  // BIG64 and the partials of SPLITK
+  return family_kernel<TileFn>(kBig64Flags, fl, rk::B64_LDS, [](auto i) -> TileFn {
+    constexpr GemmFlags f = kBig64Flags[decltype(i)::value];
+    return conv_gemm_big64_kernel<f.f32, f.fastk, f.packed, f.buf, f.epi, f.stg>;
+  });
+}
+
+// Launches what gemm_route chose: once (SPLITK: the partials and their reduce).
 static int conv_gemm_impl(const bf16_t* X, const bf16_t* W, const float* bias, const bf16_t* aux,
                           const bf16_t* resid, const int64_t* lens, void* Y, int out_f32, int B, int L, int Cin,
                           int ks, int dil, int pad, int N, int act, int ldy, const int* rinfo, EpiX ex, hipStream_t s,
                           bool bnh = false, int ksplit = 0) {
-  if (Cin % 8 != 0) return -2;
-  if ((long)B * L == 0 || N == 0) return 0;
+  GemmProblem p;
+  p.M = (long)B * L == 0 ? 0 : B * L; p.N = N; p.Cin = Cin; p.ks = ks; p.pad = pad;
+  p.ldy = ldy; p.act = act; p.ksplit = ksplit; p.out_f32 = out_f32 != 0;
+  p.bias = bias; p.aux = aux; p.resid = resid; p.lens = lens; p.rinfo = rinfo;
+  p.bnh = bnh; p.mask_in = ex.mask_in; p.mask_out = ex.mask_out; p.acc = ex.acc; p.y2 = ex.y2;
+  p.post_act = ex.post_act; p.scale_one = ex.scale == 1.f; p.bn_stats = ex.bn_stats; p.bn_part = ex.bn_part;
+  const GemmRoute r = gemm_route(p, g_knobs, device_cus());
+  if (r.kind == GEMM_NONE) return r.rc;
   ConvGeom g = make_geom(B, L, Cin, ks, dil, pad, N);
   g.rinfo = reinterpret_cast<const int2*>(rinfo);
-  if (ksplit > 0 && ks == 3 && Cin % 64 == 0 && ksplit % 256 == 0 && ksplit < N) g.ksplit = ksplit;
-  const int nwg = ((g.M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  const size_t lds = (size_t)BM * CSTRIDE * 4;  // >= 2 stages x (A+B) = 64 KiB
-  static bool lds_set = false;
-  if (!lds_set) {
-    allow_lds(conv_gemm_kernel<true, false>, lds);
-    allow_lds(conv_gemm_kernel<false, false>, lds);
-    lds_set = true;
-  }
-  // register epilogue needs N % 4 == 0 and an 8-B aligned ldy; LDS-staged epilogue otherwise
-  const bool reg = (N % 4 == 0) && (ldy % 4 == 0) && !g_force_lds_epilogue;
-  const size_t lds_reg = (size_t)2 * 2 * BM * BK * 2;
-  int variant = g_gemm_variant;
-  // measured on MI355X (tools/bench_kernels.py): the 256x256 tile with a BK=64 double buffer wins for
-  // every N >= 256 shape (+3..15 % over the 256x128 ring, +4..8 % over 256x256 with a BK=32 4-stage ring);
-  // the 256x128 ring for narrower N when K-slabs are tap-aligned, LDS-DMA 128x128 otherwise
-  if (variant < 0) variant = N >= 256 ? 4 : (Cin % BK == 0) ? 2 : 1;
-  // Few 256x256 tiles (encoder / variance-predictor GEMMs at M = B*T ~ 5k-30k rows with N = 256): the
-  // big tile leaves most of the 256 CUs idle; the 256x128 ring (or the 128x128 LDS-DMA kernel) doubles
-  // (quadruples) the tile count.  Measured at M = 14k (tools/exp_small_m.py): -20..36 % time for every
-  // N = 256 shape (k9 dgrad 219 -> 141 us), while N >= 768 keeps the 256x256 tile.
-  if (g_gemm_variant < 0 && N >= 256 && N <= 256 && ((g.M + BG - 1) / BG) * ((N + BG - 1) / BG) <= 64)
-    variant = (Cin % BK == 0) ? 2 : 1;
-  // (A/B) the 256x128 ring also for short-K GEMMs with more tiles (K <= g_ring_maxk, N <= g_ring_maxn)
-  if (g_gemm_variant < 0 && g_ring_maxk > 0 && N >= 256 && N <= g_ring_maxn && g.K <= g_ring_maxk &&
-      Cin % BK == 0)
-    variant = 2;
-  // Skinny M (<= g_skinny_maxm rows): 16 x 16 output tiles, k split over the block's waves (skinny_gemm_kernel)
-  if (g_skinny && g.M <= g_skinny_maxm && (Cin % 32 == 0 || g_skinny_any_cin) && N % 16 == 0 && !bnh && !ex.mask_out && !ex.mask_in &&
-      act >= 0 && (ex.post_act == 0 || ex.post_act == ACT_LRELU) && (!out_f32 || !(ex.acc || ex.y2 || ex.post_act ||
-      ex.scale != 1.f))) {
-    const dim3 grid(N / 16, (g.M + 15) / 16);
-    const bool w8 = g_skinny_w8 > 0 && g.K / 32 >= g_skinny_w8;  // long K: 8 waves split it (shorter chains)
-    if (Cin % 32 == 0) {
-      if (w8)
-        hipLaunchKernelGGL((skinny_gemm_kernel<8, true>), grid, dim3(512), 0, s, X, W, bias, aux, resid, lens, Y,
-                           out_f32, g, act, ldy, ex);
-      else
-        hipLaunchKernelGGL((skinny_gemm_kernel<4, true>), grid, dim3(256), 0, s, X, W, bias, aux, resid, lens, Y,
-                           out_f32, g, act, ldy, ex);
-    } else {  // Cin % 8 == 0 (conv_pre / PostNet conv 0 over 80 mel channels, the GST's first im2col layer)
-      if (w8)
-        hipLaunchKernelGGL((skinny_gemm_kernel<8, false>), grid, dim3(512), 0, s, X, W, bias, aux, resid, lens, Y,
-                           out_f32, g, act, ldy, ex);
-      else
-        hipLaunchKernelGGL((skinny_gemm_kernel<4, false>), grid, dim3(256), 0, s, X, W, bias, aux, resid, lens, Y,
-                           out_f32, g, act, ldy, ex);
+  g.ksplit = r.ksplit;
+  const dim3 grid(r.grid_x, r.grid_y), block(r.block);
+  switch (r.kind) {
+    case GEMM_SKINNY: {
+      const SkinnyFn fn = family_kernel<SkinnyFn>(kSkinnyFlags, r.fl, r.lds, [](auto i) -> SkinnyFn {
+        constexpr GemmFlags f = kSkinnyFlags[decltype(i)::value];
+        return skinny_gemm_kernel<f.waves, f.aligned>;
+      });
+      if (!fn) return -5;
+      hipLaunchKernelGGL(fn, grid, block, r.lds, s, X, W, bias, aux, resid, lens, Y, out_f32, g, act, ldy, ex);
+      break;
     }
-    return (int)hipGetLastError();
-  }
-  // Split-K for few 256x256 tiles with a long K (encoder-sized M, k = 9 data gradients, K = 9216):
-  // S slices of the k range as extra blocks writing fp32 partials, one fixed-order reduce kernel
-  // applies the epilogue.  Measured (tools/exp_splitk.py) on the tile-poor shapes only.
-  {
-    const int tiles = ((g.M + BG - 1) / BG) * ((N + BG - 1) / BG);
-    const int nk64 = (g.K + 63) / 64;
-    // the reduce applies EpiX's accumulate / scale / y2 / post activation (bf16 output, as the big64 epilogue)
-    const bool xon = ex.acc || ex.y2 || ex.post_act || ex.scale != 1.f;
-    const bool plain = !(ex.mask_out || ex.mask_in || bnh) && (!xon || (!out_f32 && (ex.post_act == 0 ||
-                                                                                     ex.post_act == ACT_LRELU)));
-    int S = 0;
-    if (g_splitk > 0) S = g_splitk;
-    else if (g_splitk < 0 && g_gemm_variant < 0 && tiles <= 128 && nk64 >= 16)
-      // as many slices as keep the split grid within ONE wave of blocks (a second partial wave
-      // costs more than it saves: M = 10800 / 43 tiles: S = 4 81 us, S = 6 111 us, unsplit 149 us)
-      S = min(min(8, g_num_cus_gemm / tiles), nk64 / 6);
-    // a handful of tiles at <= 1024 rows (batch-1 inference: one utterance's phonemes / frames / first vocoder
-    // stages) is a serial chain of k-steps on a few CUs: shorter slices (>= g_splitk_tiny k-steps each), also
-    // for the shorter K of the k = 3 convs
-    if (g_splitk < 0 && g_gemm_variant < 0 && g_splitk_tiny > 0 && tiles <= 8 && g.M <= 1024 &&
-        nk64 >= 2 * g_splitk_tiny)
-      S = max(S, min(8, nk64 / g_splitk_tiny));
-    if (S > 1 && plain && reg && N >= 256 && (N % 8) == 0 && ldy == N && act >= 0 && (ldy % 8) == 0) {
-      void* ws = splitk_workspace(s, (size_t)S * g.M * N * sizeof(float));
+    case GEMM_SPLITK: {
+      const TileFn fn = big64_kernel(r.fl);
+      if (!fn) return -5;
+      void* ws = splitk_workspace(s, (size_t)r.S * g.M * N * sizeof(float));
       if (!ws) return -4;
-      static bool sk_set = false;
-      if (!sk_set) {
-        allow_lds(conv_gemm_big64_kernel<true, true, false>, B64_LDS);
-        allow_lds(conv_gemm_big64_kernel<true, false, false>, B64_LDS);
-        allow_lds(conv_gemm_big64_kernel<true, true, true>, B64_LDS);
-        allow_lds(conv_gemm_big64_kernel<true, false, true>, B64_LDS);
-        allow_lds(conv_gemm_big64_kernel<true, true, false, true>, B64_LDS);
-        allow_lds(conv_gemm_big64_kernel<true, true, true, true>, B64_LDS);
-        sk_set = true;
-      }
-      const bool fastk = (Cin % 64) == 0;
-      const bool bf = fastk && big64_buf_ok(g);
-      auto kfn = g.rinfo ? (bf ? conv_gemm_big64_kernel<true, true, true, true>
-                               : fastk ? conv_gemm_big64_kernel<true, true, true> : conv_gemm_big64_kernel<true, false, true>)
-                         : (bf ? conv_gemm_big64_kernel<true, true, false, true>
-                               : fastk ? conv_gemm_big64_kernel<true, true, false> : conv_gemm_big64_kernel<true, false, false>);
-      hipLaunchKernelGGL(kfn, dim3(tiles, S), dim3(NT3), B64_LDS, s, X, W, nullptr, nullptr, nullptr, nullptr,
-                         ws, g, 0, N, EpiX{});
+      hipLaunchKernelGGL(fn, grid, block, r.lds, s, X, W, nullptr, nullptr, nullptr, nullptr, ws, g, 0, N, EpiX{});
       const long nthr = (long)g.M * (N / 8);
       hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(nthr, 256)), dim3(256), 0, s,
-                         reinterpret_cast<const float*>(ws), S, (long)g.M, N, bias, aux, resid, lens, g.L,
+                         reinterpret_cast<const float*>(ws), r.S, (long)g.M, N, bias, aux, resid, lens, g.L,
                          act, out_f32, Y, ex.acc, ex.y2, ex.scale, ex.post_act);
-      return (int)hipGetLastError();
+      break;
     }
-  }
-  // K = 256 Linear layers (QKV, attention fc and its data gradient, the w_2 data gradient with its ReLU
-  // bitmask): the weight-stationary streaming kernel, one block per CU.  Only the epilogue forms the training
-  // step uses at K = 256 (bias, mask_in, bf16 out, ldy == N); everything else stays on the tile kernels.
-  // Rows: every byte offset of its descriptors (two chunks of read-ahead included) stays below 2^31.
-  // Auto rule, measured against the kernel each shape ran on before (tools/bench_kernels.py --k256, 5 interleaved
-  // rounds, routed only where every round of the new kernel beat every round of the old;
-  // profiles/k256_stream.txt; us old -> new):
-  //   N >= 1024 (ReLU-mask dgrad)  from 2048 rows: 100352 rows 147 -> 80, 14336 rows 22.4 -> 21.5, 2048 19.5 -> 12.3
-  //   N = 512 / 768 (QKV)          from 28672 rows: 100352 rows 77 -> 55, 28672 26.6 -> 23; 8192 / 14336 rows LOSE
-  //                                (13.8 -> 15.5, 15.8 -> 18.3: 3 groups x 85 blocks of ~3 chunks, prologue-bound)
-  //   N = 256 (fc fwd / dgrad)     <= 64 tiles, where the 256x128 ring ran (14336 rows 14.6 -> 13.1, 2048 13.1 -> 10.9),
-  //                                and from 1.5 waves of 256-row tiles (100352 rows 29.3 -> 27.7, 30.0 -> 28.6 in
-  //                                a second session); up to one wave the balanced 256x256 tiles win (28672 rows
-  //                                13.8 -> 16.0, 50176 15.3 -> 19.4), between 1 and 1.5 waves it is mixed (69632 rows
-  //                                26.5 -> 23.5 every round, 81920 rows 27.7 -> 27.3 with one round behind)
-  // Below 2048 rows nothing was measured (the skinny kernel takes <= 1024).
-  const int k256_tiles = (g.M + BG - 1) / BG;
-  const bool k256_auto = g_gemm_variant < 0 && g.M >= 2048 &&
-                         (N >= 1024 || (N >= 512 && g.M >= g_k256_min_rows) ||
-                          (N == 256 && (k256_tiles <= 64 || 2 * k256_tiles >= 3 * device_cus())));
-  if (g_gemm_k256 != 0 && ks == 1 && Cin == 256 && N >= 256 && N % 256 == 0 && !out_f32 && !aux && !resid && !lens &&
-      !rinfo && !bnh && ksplit == 0 && act == 0 && ldy == N && reg && !ex.acc && !ex.y2 && !ex.post_act &&
-      ex.scale == 1.f && !ex.mask_out && !ex.bn_stats && !ex.bn_part &&
-      ((long)g.M + 4 * K256_ROWS) * (N > 256 ? N : 256) * 2 < (1L << 31) &&
-      (g_gemm_k256 > 0 || k256_auto)) {
-    static bool k2_set = false;
-    if (!k2_set) {
-      allow_lds(conv_gemm_k256_kernel<false, false>, K2_LDS);
-      allow_lds(conv_gemm_k256_kernel<false, true>, K2_LDS);
-      allow_lds(conv_gemm_k256_kernel<true, false>, K2_LDS);
-      allow_lds(conv_gemm_k256_kernel<true, true>, K2_LDS);
-      k2_set = true;
+    case GEMM_K256: {
+      const K256Fn fn = family_kernel<K256Fn>(kK256Flags, r.fl, r.lds, [](auto i) -> K256Fn {
+        constexpr GemmFlags f = kK256Flags[decltype(i)::value];
+        return conv_gemm_k256_kernel<f.mask, f.has_bias>;
+      });
+      if (!fn) return -5;
+      hipLaunchKernelGGL(fn, grid, block, r.lds, s, X, W, bias, ex.mask_in, reinterpret_cast<bf16_t*>(Y), g.M, N, r.nb);
+      break;
     }
-    const int ng = N / 256;
-    const int nb = k256_blocks_per_group(g_k256_blocks > 0 ? g_k256_blocks : device_cus(), ng, k256_chunks(g.M));
-    auto kfn = ex.mask_in ? (bias ? conv_gemm_k256_kernel<true, true> : conv_gemm_k256_kernel<true, false>)
-                          : (bias ? conv_gemm_k256_kernel<false, true> : conv_gemm_k256_kernel<false, false>);
-    hipLaunchKernelGGL(kfn, dim3(nb * ng), dim3(NT3), K2_LDS, s, X, W, bias, ex.mask_in, reinterpret_cast<bf16_t*>(Y),
-                       g.M, N, nb);
-    return (int)hipGetLastError();
-  }
-  if (bnh) {  // BatchNorm-backward head (EpiX aliases: acc = bn_h, ln_w = stats, mean = partials): big64 only
-    if (N < 256 || (N % 8) || ldy != N || out_f32 || !reg || act != 0 || ex.post_act == 2 || aux || resid || lens || !ex.acc ||
-        !ex.bn_stats || !ex.bn_part || rinfo || ex.y2 || ex.mask_out || ex.mask_in)
-      return -3;
-    variant = 4;
-  } else {
-  if (ex.mask_out || ex.mask_in) {  // the bitmask lives in the big64 LDS-staged epilogue only
-    if (N < 256 || (N % 8) || ldy != N || out_f32 || !reg || act < 0) return -3;
-    if (ex.mask_out && act != ACT_RELU) return -3;
-    variant = 4;
-  }
-  const bool xon = ex.acc || ex.y2 || ex.post_act || ex.scale != 1.f;
-  if (xon) {  // only the big64 (LDS-staged bf16 epilogue) and ring kernels implement EpiX
-    if (out_f32 || !reg || (N % 8) || (ldy % 8) || act < 0) return -3;
-    if (N >= 256) variant = 4;
-    else if (variant != 2) return -3;
-  }
-  }  // !bnh
-  if (reg && variant == 4 && N >= 256) {
-    static bool b64_set = false;
-    if (!b64_set) {
-      allow_lds(conv_gemm_big64_kernel<true, true, false>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, false>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<true, false, false>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, false, false>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<true, true, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<true, false, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, false, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<true, true, false, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, false, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<true, true, true, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, true, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, false, true, EPI_BNH>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, false, true, EPI_BNH, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, false, false, EPI_BNH>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, false, false, false, EPI_BNH>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, false, true, EPI_GEN, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, true, true, EPI_GEN, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<true, true, false, true, EPI_GEN, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<true, true, true, true, EPI_GEN, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, false, true, EPI_MASK>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, true, true, EPI_MASK>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, false, true, EPI_MASK, true>, B64_LDS);
-      allow_lds(conv_gemm_big64_kernel<false, true, true, true, EPI_MASK, true>, B64_LDS);
-      b64_set = true;
+    case GEMM_BIG64:
+    case GEMM_RING: {
+      TileFn fn;
+      if (r.kind == GEMM_BIG64)
+        fn = big64_kernel(r.fl);
+      else
+        fn = family_kernel<TileFn>(kRingFlags, r.fl, r.lds, [](auto i) -> TileFn {
+          constexpr GemmFlags f = kRingFlags[decltype(i)::value];
+          return conv_gemm_ring_kernel<f.f32, f.fastk, f.packed, f.buf>;
+        });
+      if (!fn) return -5;
+      hipLaunchKernelGGL(fn, grid, block, r.lds, s, X, W, bias, aux, resid, lens, Y, g, act, ldy, ex);
+      break;
     }
-    const int nwgb = ((g.M + BG - 1) / BG) * ((N + BG - 1) / BG);
-    const bool fastk = (Cin % 64) == 0;
-    const size_t LB = B64_LDS;
-    // the ReLU-mask data gradient with nothing else in its epilogue: mask bytes prefetched (EPI_MASK)
-    const bool mask_pre = ex.mask_in && !ex.mask_out && !bnh && !aux && !resid && !lens && !ex.acc && !ex.y2 &&
-                          !ex.post_act && ex.scale == 1.f && !out_f32 && act >= 0 && ldy == N;
-#define B64_LAUNCH(F32, FK)                                                                              \
-    do {                                                                                                 \
-      auto kfn = g.rinfo ? conv_gemm_big64_kernel<F32, FK, true, BF> : conv_gemm_big64_kernel<F32, FK, false, BF>; \
-      const bool stg_ = g_gemm_stg && g.K >= 512;                                                        \
-      int grid_x = nwgb;                                                                                 \
-      if constexpr (!F32) {                                                                              \
-        if (bnh) kfn = conv_gemm_big64_kernel<false, FK, false, BF, EPI_BNH>;                           \
-      }                                                                                                  \
-      if constexpr (BF) {                                                                                \
-        if (stg_ && !bnh)                                                                                \
-          kfn = g.rinfo ? conv_gemm_big64_kernel<F32, true, true, true, EPI_GEN, true>                   \
-                        : conv_gemm_big64_kernel<F32, true, false, true, EPI_GEN, true>;                 \
-        if constexpr (!F32) {                                                                            \
-          if (stg_ && bnh && g_gemm_bnh_stg) kfn = conv_gemm_big64_kernel<false, true, false, true, EPI_BNH, true>; \
-        }                                                                                                \
-        if constexpr (!F32) {                                                                            \
-          if (g_gemm_mask_pre && mask_pre)                                                               \
-            kfn = stg_ ? (g.rinfo ? conv_gemm_big64_kernel<false, true, true, true, EPI_MASK, true>       \
-                                  : conv_gemm_big64_kernel<false, true, false, true, EPI_MASK, true>)    \
-                       : (g.rinfo ? conv_gemm_big64_kernel<false, true, true, true, EPI_MASK>             \
-                                  : conv_gemm_big64_kernel<false, true, false, true, EPI_MASK>);         \
-        }                                                                                                \
-      }                                                                                                  \
-      hipLaunchKernelGGL(kfn, dim3(grid_x), dim3(NT3), LB, s, X, W, bias, aux, resid, lens, Y, g, act, ldy, ex); \
-    } while (0)
-    const bool bf = fastk && big64_buf_ok(g);
-    if (out_f32) {
-      if (bf) { constexpr bool BF = true; B64_LAUNCH(true, true); }
-      else if (fastk) { constexpr bool BF = false; B64_LAUNCH(true, true); }
-      else { constexpr bool BF = false; B64_LAUNCH(true, false); }
-    } else {
-      if (bf) { constexpr bool BF = true; B64_LAUNCH(false, true); }
-      else if (fastk) { constexpr bool BF = false; B64_LAUNCH(false, true); }
-      else { constexpr bool BF = false; B64_LAUNCH(false, false); }
+    case GEMM_GLDS:
+    case GEMM_REG:
+    case GEMM_LDS_EPI: {  // the 128x128 kernels; only the LDS-staged epilogue needs more than 64 KiB
+      C128Fn fn;
+      if (r.kind == GEMM_GLDS)
+        fn = family_kernel<C128Fn>(kC128Flags, r.fl, r.lds, [](auto i) -> C128Fn {
+          return conv_gemm_glds_kernel<kC128Flags[decltype(i)::value].f32>;
+        });
+      else if (r.kind == GEMM_REG)
+        fn = family_kernel<C128Fn>(kC128Flags, r.fl, r.lds, [](auto i) -> C128Fn {
+          return conv_gemm_kernel<kC128Flags[decltype(i)::value].f32, true>;
+        });
+      else
+        fn = family_kernel<C128Fn>(kC128Flags, r.fl, r.lds, [](auto i) -> C128Fn {
+          return conv_gemm_kernel<kC128Flags[decltype(i)::value].f32, false>;
+        });
+      if (!fn) return -5;
+      hipLaunchKernelGGL(fn, grid, block, r.lds, s, X, W, bias, aux, resid, lens, Y, g, act, ldy);
+      break;
     }
-#undef B64_LAUNCH
-  } else if (reg && variant >= 2) {
-    static bool ring_set = false;
-    if (!ring_set) {
-      allow_lds(conv_gemm_ring_kernel<true, true, false>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<false, true, false>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<true, false, false>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<false, false, false>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<true, true, true>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<false, true, true>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<true, false, true>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<false, false, true>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<true, true, false, true>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<false, true, false, true>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<true, true, true, true>, NSTAGE * STAGE_BYTES);
-      allow_lds(conv_gemm_ring_kernel<false, true, true, true>, NSTAGE * STAGE_BYTES);
-      ring_set = true;
-    }
-    const int nwg3 = ((g.M + BM3 - 1) / BM3) * ((N + BN - 1) / BN);
-    const bool fastk = (Cin % BK) == 0;
-    const size_t L3 = NSTAGE * STAGE_BYTES;
-#define RING_LAUNCH(F32, FK)                                                                        \
-    do {                                                                                            \
-      auto kfn = g.rinfo ? conv_gemm_ring_kernel<F32, FK, true, BF> : conv_gemm_ring_kernel<F32, FK, false, BF>; \
-      hipLaunchKernelGGL(kfn, dim3(nwg3), dim3(NT3), L3, s, X, W, bias, aux, resid, lens, Y, g, act, ldy, ex); \
-    } while (0)
-    const bool bf = fastk && big64_buf_ok(g);
-    if (out_f32) {
-      if (bf) { constexpr bool BF = true; RING_LAUNCH(true, true); }
-      else if (fastk) { constexpr bool BF = false; RING_LAUNCH(true, true); }
-      else { constexpr bool BF = false; RING_LAUNCH(true, false); }
-    } else {
-      if (bf) { constexpr bool BF = true; RING_LAUNCH(false, true); }
-      else if (fastk) { constexpr bool BF = false; RING_LAUNCH(false, true); }
-      else { constexpr bool BF = false; RING_LAUNCH(false, false); }
-    }
-#undef RING_LAUNCH
-  } else if (reg && variant == 1) {
-    if (out_f32)
-      hipLaunchKernelGGL((conv_gemm_glds_kernel<true>), dim3(nwg), dim3(NT), lds_reg, s, X, W, bias, aux, resid, lens,
-                         Y, g, act, ldy);
-    else
-      hipLaunchKernelGGL((conv_gemm_glds_kernel<false>), dim3(nwg), dim3(NT), lds_reg, s, X, W, bias, aux, resid, lens,
-                         Y, g, act, ldy);
-  } else if (reg) {
-    if (out_f32)
-      hipLaunchKernelGGL((conv_gemm_kernel<true, true>), dim3(nwg), dim3(NT), lds_reg, s, X, W, bias, aux, resid, lens,
-                         Y, g, act, ldy);
-    else
-      hipLaunchKernelGGL((conv_gemm_kernel<false, true>), dim3(nwg), dim3(NT), lds_reg, s, X, W, bias, aux, resid, lens,
-                         Y, g, act, ldy);
-  } else if (out_f32) {
-    hipLaunchKernelGGL((conv_gemm_kernel<true, false>), dim3(nwg), dim3(NT), lds, s, X, W, bias, aux, resid, lens, Y, g,
-                       act, ldy);
-  } else {
-    hipLaunchKernelGGL((conv_gemm_kernel<false, false>), dim3(nwg), dim3(NT), lds, s, X, W, bias, aux, resid, lens, Y,
-                       g, act, ldy);
+    default:
+      return -5;
   }
   return (int)hipGetLastError();
 }
@@ -3258,15 +3077,6 @@ SSAMD_API int ssamd_conv_gemm_mask(const bf16_t* X, const bf16_t* W, const float
   return conv_gemm_impl(X, W, bias, nullptr, nullptr, nullptr, Y, 0, B, L, Cin, ks, dil, pad, N, act, N, rinfo, ex, s);
 }
 
-static int g_wgrad_imm = -1;  // -1 auto, 0 / 1: force the big64 wgrad read schedule
-SSAMD_API void ssamd_wgrad_set_imm(int v) { g_wgrad_imm = v; }
-static int g_wgrad_buf = 1;  // big64 wgrad LDS-DMA through buffer descriptors (0: flat global_load_lds)
-SSAMD_API void ssamd_wgrad_set_buf(int v) { g_wgrad_buf = v; }
-// big64 wgrad (buffer-descriptor path) ping-pong main loop: -1 auto = on packed rows (decoder k9 wgrad
-// 646 -> 519 us vs 718 before, tools/exp_wgrad_pp.py), off on plain rows (PostNet k5 -14 %)
-static int g_wgrad_pp = -1;
-SSAMD_API void ssamd_wgrad_set_pp(int v) { g_wgrad_pp = v; }
-
 // Workspace: splits * N * ks*Cin floats.  Returns the number of splits used via *splits_used.
 // ws: splits*N*ks*Cin (+ splits*N when db != null) floats.  db (optional): fused bias gradient.
 static void launch_reduce(const float* ws, float* dW, const float* bws, float* db, int splits, int N, int Cin, int ks,
@@ -3286,144 +3096,51 @@ static void launch_reduce(const float* ws, float* dW, const float* bws, float* d
                      ks, nb_main);
 }
 
-// Split-M count of the 256x256 weight-gradient kernel (one block per CU): the blocks run in
-// ceil(tiles * S / CUs) rounds of ceil(M / S / 64) row steps each, and every split adds a 256x256
-// fp32 slab to write and reduce (~8 % of a 64-row step per slab tile).  The old fixed target of 512
-// blocks left partial rounds (packed k9 wgrad: 36 tiles x 15 = 540 blocks = 2.1 rounds -> 3) and,
-// capped by the 128x128 kernels' split limit, single-tile weights ran on 64 CUs.
-static int g_cus_dev[64];
-static int device_cus() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (!g_cus_dev[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    g_cus_dev[dev] = n;
-  }
-  return g_cus_dev[dev];
-}
-static int g_wgrad_blocks = 0;   // > 0: fixed split-M target (blocks per launch) instead of the cost model
-// > 0: plan the split-M rounds for this many CUs instead of the device's (a weight gradient on the side
-// stream then leaves the other CUs to the data-gradient chain instead of holding every CU's LDS)
-// The budget applies to launches on ONE stream (the weight-gradient side stream): a main-stream weight
-// gradient (first step, --no-side-wgrad) keeps the whole-device plan, so the split-M count -- and with it
-// the fp32 reduction order -- of a main-stream launch does not depend on the side-stream setting.
-static int g_wgrad_cus = 0;
-static hipStream_t g_wgrad_cus_stream = nullptr;
-static int choose_wgrad_splits(int tiles, int M, int max_splits, long ws_splits, int cus) {
-  const int steps_all = (M + 63) / 64;
-  int smax = max_splits;
-  if (smax > steps_all / 4) smax = steps_all / 4 > 0 ? steps_all / 4 : 1;  // >= 4 row steps per split
-  if ((long)smax > ws_splits) smax = (int)ws_splits;
-  if (smax < 1) return (int)(ws_splits >= 1 ? 1 : 0);
-  if (g_wgrad_blocks > 0) {
-    const int sp = (g_wgrad_blocks + tiles - 1) / tiles;
-    return sp < smax ? sp : smax;
-  }
-  int best = 1;
-  double best_c = 1e30;
-  for (int sp = 1; sp <= smax; ++sp) {
-    const long rounds = ((long)tiles * sp + cus - 1) / cus;
-    const long steps = (steps_all + sp - 1) / sp;
-    const double c = (double)rounds * (double)steps + 0.08 * (double)sp * tiles;
-    if (c < best_c - 1e-9) { best_c = c; best = sp; }
-  }
-  return best;
-}
-
-static int g_wgrad_variant = -1;  // -1 auto (256x256 BK=64 when it applies), 0: force the 128x128 kernels
-SSAMD_API void ssamd_wgrad_set_blocks(int b) { g_wgrad_blocks = b > 0 ? b : 0; }
-SSAMD_API void ssamd_wgrad_set_cus(hipStream_t s, int n) {
-  g_wgrad_cus = n > 0 ? n : 0;
-  g_wgrad_cus_stream = s;
-}
-SSAMD_API void ssamd_wgrad_set_variant(int v) { g_wgrad_variant = v; }
-
 SSAMD_API int ssamd_conv_wgrad(const bf16_t* X, const bf16_t* dY, float* ws, long ws_floats, float* dW, float* db,
                                int B, int L, int Cin, int ks, int dil, int pad, int N, int max_splits, const int* rinfo,
                                const int64_t* cu, int nseq, hipStream_t s) {
-  if (Cin % 8 != 0 || N % 8 != 0) return -2;
+  WgradProblem p;
+  p.M = B * L; p.N = N; p.Cin = Cin; p.ks = ks; p.pad = pad;
+  p.packed = rinfo != nullptr; p.cu = cu != nullptr; p.nseq = nseq; p.max_splits = max_splits; p.ws_floats = ws_floats;
+  const bool on = g_wgrad_cus_stream == reinterpret_cast<hipStream_t>(-1) || s == g_wgrad_cus_stream;
+  const WgradRoute r = wgrad_route(p, g_knobs, (g_knobs.wgrad_cus > 0 && on) ? g_knobs.wgrad_cus : device_cus());
+  if (r.rc < 0) return r.rc;
   ConvGeom g = make_geom(B, L, Cin, ks, dil, pad, N);
   g.rinfo = reinterpret_cast<const int2*>(rinfo);
   g.cu = cu;
   g.nseq = nseq;
-  g.prio = g_wgrad_prio;
+  g.prio = g_knobs.wgrad_prio;
   const long slab = (long)N * g.K;
-  if (g.M == 0) {
-    hipMemsetAsync(dW, 0, slab * sizeof(float), s);
-    if (db) hipMemsetAsync(db, 0, N * sizeof(float), s);
-    return (int)hipGetLastError();
+  using WgradFn = void (*)(const bf16_t*, const bf16_t*, float*, float*, ConvGeom, int);
+  WgradFn fn;
+  switch (r.kind) {
+    case WGRAD_NONE:  // no rows
+      hipMemsetAsync(dW, 0, slab * sizeof(float), s);
+      if (db) hipMemsetAsync(db, 0, N * sizeof(float), s);
+      return (int)hipGetLastError();
+    case WGRAD_BIG64:
+      fn = family_kernel<WgradFn>(kWgradBig64Flags, r.fl, rk::WB64_LDS_MAX, [](auto i) -> WgradFn {
+        constexpr WgradFlags f = kWgradBig64Flags[decltype(i)::value];
+        return conv_wgrad_big64_kernel<f.packed, f.imm, f.buf, f.pp>;
+      });
+      break;
+    case WGRAD_REG:
+      fn = family_kernel<WgradFn>(kWgrad128Flags, r.fl, r.lds, [](auto i) -> WgradFn {
+        return conv_wgrad_reg_kernel<kWgrad128Flags[decltype(i)::value].packed>;
+      });
+      break;
+    case WGRAD_DMA:
+      fn = family_kernel<WgradFn>(kWgrad128Flags, r.fl, r.lds, [](auto i) -> WgradFn {
+        return conv_wgrad_kernel<kWgrad128Flags[decltype(i)::value].packed>;
+      });
+      break;
+    default:
+      return -5;
   }
-  const bool packed = rinfo != nullptr;
-  // 256x256 kernel (split-M slabs + fixed-order reduce) when there are >= 2 output tiles; variant 0
-  // forces the 128x128 kernels (the choice for single-tile and narrow problems)
-  const bool big = g_wgrad_variant != 0 && N >= 256 && g.K >= 256 && (long)N * g.K >= 2L * 256 * 256 &&
-                   (!packed || (cu != nullptr && nseq > 0 && nseq < 8192));
-  if (big) {
-    static bool b64_set = false;
-    if (!b64_set) {
-      allow_lds(conv_wgrad_big64_kernel<false, false, false>, 160 * 1024);
-      allow_lds(conv_wgrad_big64_kernel<true, false, false>, 160 * 1024);
-      allow_lds(conv_wgrad_big64_kernel<false, true, false>, 160 * 1024);
-      allow_lds(conv_wgrad_big64_kernel<true, true, false>, 160 * 1024);
-      allow_lds(conv_wgrad_big64_kernel<false, false, true>, 160 * 1024);
-      allow_lds(conv_wgrad_big64_kernel<true, false, true>, 160 * 1024);
-      allow_lds(conv_wgrad_big64_kernel<false, true, true>, 160 * 1024);
-      allow_lds(conv_wgrad_big64_kernel<true, true, true>, 160 * 1024);
-      allow_lds(conv_wgrad_big64_kernel<false, false, true, true>, 160 * 1024);
-      allow_lds(conv_wgrad_big64_kernel<true, false, true, true>, 160 * 1024);
-      b64_set = true;
-    }
-    const int tiles = ((N + 255) / 256) * ((g.K + 255) / 256);
-    const bool on = g_wgrad_cus_stream == reinterpret_cast<hipStream_t>(-1) || s == g_wgrad_cus_stream;
-    const int cus = (g_wgrad_cus > 0 && on) ? g_wgrad_cus : device_cus();
-    int splits = choose_wgrad_splits(tiles, g.M, max_splits, ws_floats / (slab + N), cus);
-    if (splits < 1) return -3;
-    int rows_per_split = (g.M + splits - 1) / splits;
-    rows_per_split = (rows_per_split + 63) / 64 * 64;
-    splits = (g.M + rows_per_split - 1) / rows_per_split;
-    float* bws = db ? ws + (long)splits * slab : nullptr;
-    size_t lds = 2 * WB64_STAGE;
-    if (lds < 128 * 1088) lds = 128 * 1088;  // the LDS-staged slab epilogue tile
-    // immediate-offset fragment reads: measured faster on packed rows (the decoder FFN), the
-    // single-wait schedule on plain rows (tools/exp_packed_wgrad.py); g_wgrad_imm overrides
-    const bool imm = g_wgrad_imm < 0 ? packed : g_wgrad_imm != 0;
-    // buffer-descriptor DMA needs every byte offset in 31 bits (out-of-range marker 0x80000000)
-    const bool bufok = g_wgrad_buf != 0 && (long)(g.M + pad) * Cin * 2 < (1L << 31) &&
-                       (long)rows_per_split * N * 2 < (1L << 31);
-    auto wb = bufok ? (packed ? (imm ? conv_wgrad_big64_kernel<true, true, true> : conv_wgrad_big64_kernel<true, false, true>)
-                              : (imm ? conv_wgrad_big64_kernel<false, true, true> : conv_wgrad_big64_kernel<false, false, true>))
-                    : (packed ? (imm ? conv_wgrad_big64_kernel<true, true, false> : conv_wgrad_big64_kernel<true, false, false>)
-                              : (imm ? conv_wgrad_big64_kernel<false, true, false> : conv_wgrad_big64_kernel<false, false, false>));
-    if (bufok && (g_wgrad_pp < 0 ? packed : g_wgrad_pp != 0))
-      wb = packed ? conv_wgrad_big64_kernel<true, false, true, true> : conv_wgrad_big64_kernel<false, false, true, true>;
-    hipLaunchKernelGGL(wb, dim3(tiles * splits), dim3(NT3), lds, s, X, dY, ws, bws, g, rows_per_split);
-    const int blocks = (int)min((slab + 255) / 256, 8192L);
-    launch_reduce(ws, dW, bws, db, splits, N, Cin, ks, blocks, s);
-    return (int)hipGetLastError();
-  }
-  const int tiles = ((N + 127) / 128) * ((g.K + 127) / 128);
-  int splits = (1536 + tiles - 1) / tiles;
-  const int max_by_rows = (g.M + 511) / 512;
-  if (splits > max_by_rows) splits = max_by_rows;
-  if (splits > max_splits) splits = max_splits;
-  if ((long)splits * (slab + N) > ws_floats) splits = (int)(ws_floats / (slab + N));
-  if (splits < 1) return -3;
-  int rows_per_split = (g.M + splits - 1) / splits;
-  rows_per_split = (rows_per_split + RB - 1) / RB * RB;
-  splits = (g.M + rows_per_split - 1) / rows_per_split;
-  float* bws = db ? ws + (long)splits * slab : nullptr;
-  auto wreg = g.rinfo ? conv_wgrad_reg_kernel<true> : conv_wgrad_reg_kernel<false>;
-  auto wdma = g.rinfo ? conv_wgrad_kernel<true> : conv_wgrad_kernel<false>;
-  if (g.K > 1024)
-    hipLaunchKernelGGL(wreg, dim3(tiles * splits), dim3(NT), 2 * 2 * RB * 256, s, X, dY, ws, bws, g,
-                       rows_per_split);
-  else
-    hipLaunchKernelGGL(wdma, dim3(tiles * splits), dim3(NT), 2 * 2 * RB * 256, s, X, dY, ws, bws, g,
-                       rows_per_split);
-  const long total = slab;
-  int blocks = (int)min((total + 255) / 256, 8192L);
-  launch_reduce(ws, dW, bws, db, splits, N, Cin, ks, blocks, s);
+  if (!fn) return -5;
+  float* bws = db ? ws + (long)r.splits * slab : nullptr;
+  hipLaunchKernelGGL(fn, dim3(r.grid_x), dim3(r.block), r.lds, s, X, dY, ws, bws, g, r.rows_per_split);
+  launch_reduce(ws, dW, bws, db, r.splits, N, Cin, ks, (int)min((slab + 255) / 256, 8192L), s);
   return (int)hipGetLastError();
 }
 
