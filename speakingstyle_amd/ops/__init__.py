@@ -492,6 +492,40 @@ def prosody_transfer(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, ener
               pitch_mode)
 
 
+def tsne_affinities(x, perplexity):
+    """Joint affinities of exact t-SNE: x [N, D] -> P [N, N], symmetric, zero diagonal, sums to 1; see
+    ``ops.reference.tsne_affinities``.  On the GPU a workgroup per row bisects beta (``csrc/k_stylemap.hip``)."""
+    fn = _hip().tsne_affinities if use_hip(x) else ref.tsne_affinities
+    return fn(x, perplexity)
+
+
+def tsne_gradient(P, y, exaggeration=1.0):
+    """The t-SNE gradient's parts at the map y [N, 2] -> (attr [N, 2], rep [N, 2], zrow [N], grad [N, 2]); see
+    ``ops.reference.tsne_gradient``."""
+    fn = _hip().tsne_gradient if use_hip(y) else ref.tsne_gradient
+    return fn(P, y, exaggeration)
+
+
+def tsne_kl(P, y):
+    """KL(P || Q) of the map y; see ``ops.reference.tsne_kl``."""
+    fn = _hip().tsne_kl if use_hip(y) else ref.tsne_kl
+    return fn(P, y)
+
+
+def tsne(x, perplexity=30.0, n_iter=750, exag_iter=250, early_exaggeration=12.0, init="pca", seed=0, kl_every=50):
+    """Exact t-SNE of x [N, D] (7 <= N <= 16384) -> (y [N, 2], kl_trace: KL after every ``kl_every`` updates and
+    after the last); see ``ops.reference.tsne``.  On the GPU the loop runs without a host synchronisation."""
+    fn = _hip().tsne if use_hip(x) else ref.tsne
+    return fn(x, perplexity, n_iter, exag_iter, early_exaggeration, init, seed, kl_every)
+
+
+def kmeans(x, k, n_iter=100, seed=0):
+    """Lloyd's k-means with a farthest-point start: x [N, D] (D <= 512), 1 <= k <= 64 -> (labels int32 [N],
+    centroids [k, D], iterations); see ``ops.reference.kmeans``."""
+    fn = _hip().kmeans if use_hip(x) else ref.kmeans
+    return fn(x, k, n_iter, seed)
+
+
 def frame_features(wav, lengths, n_fft, hop, window, basis, clip=1e-5, clip_wave=False):
     """Log-mel and energy of packed utterances (layout and frame counts of ``yin``; ``window`` the n_fft-point analysis
     window, ``basis`` [n_mel, n_fft / 2 + 1]; ``clip_wave`` clamps the samples to [-1, 1] in the gather) -> (mel [R,

@@ -3397,6 +3397,135 @@ def prosody_transfer(path, path_len, src_dur, src_lens, x_lens, y_lens, f0, ener
     return rec_dur, pitch, en, voiced, ok
 
 
+# ------------------------------------------------------------------------ style map (csrc/k_stylemap.hip)
+_SIGS.update({"ssamd_tsne_aff_ws": [I], "ssamd_tsne_affinities": [P, I, I, F, P, P, I, P],
+              "ssamd_tsne_iter_ws": [I], "ssamd_tsne_iter": [P, P, I, P, F, F, F, P, P, P, P, I, P],
+              "ssamd_kmeans_ws": [I, I, I], "ssamd_kmeans_init": [P, I, I, I, I, P, P, P],
+              "ssamd_kmeans_step": [P, I, I, I, P, P, P, P, P]})
+_RESTYPES.update({"ssamd_tsne_aff_ws": L_, "ssamd_tsne_iter_ws": L_, "ssamd_kmeans_ws": L_})
+
+
+def _f32_points(x, name):
+    x = x.detach().float().contiguous()
+    _need(x, torch.float32, name)
+    return x
+
+
+@torch.no_grad()
+def tsne_affinities(x, perplexity, joint=True):
+    """``ops.reference.tsne_affinities`` on the GPU (fp32): distances, a workgroup per row for the bisection, the
+    fixed-order sum and the in-place symmetrisation -> P [N, N].  ``joint=False`` stops at the row-normalised
+    conditional P (``ops.reference.tsne_conditional``)."""
+    N, D = ref.tsne_check(x, perplexity)
+    x = _f32_points(x, "tsne_affinities.x")
+    Pm = torch.empty(N, N, device=x.device, dtype=torch.float32)
+    ws = torch.empty(int(lib().ssamd_tsne_aff_ws(N)), device=x.device, dtype=torch.float32)
+    rc = lib().ssamd_tsne_affinities(_ptr(x), N, D, float(math.log(perplexity)), _ptr(Pm), _ptr(ws), int(bool(joint)),
+                                     _stream())
+    _check(rc, "ssamd_tsne_affinities")
+    return Pm
+
+
+def _tsne_operands(P, y):
+    if P.dim() != 2 or P.shape[0] != P.shape[1] or tuple(y.shape) != (P.shape[0], 2):
+        raise ValueError(f"tsne: P must be [N, N] and y [N, 2], got {tuple(P.shape)} and {tuple(y.shape)}")
+    N = P.shape[0]
+    if N < 2 or N > ref.TSNE_MAX_N:
+        raise ValueError(f"tsne: N = {N} is outside 2 .. TSNE_MAX_N = {ref.TSNE_MAX_N}")
+    P = _f32_points(P, "tsne.P")
+    ws = torch.empty(int(lib().ssamd_tsne_iter_ws(N)), device=P.device, dtype=torch.float32)
+    return N, P, ws
+
+
+@torch.no_grad()
+def tsne_gradient(P, y, exaggeration=1.0):
+    """``ops.reference.tsne_gradient`` on the GPU -> (attr [N, 2], rep [N, 2], zrow [N], grad [N, 2])."""
+    N, P, ws = _tsne_operands(P, y)
+    y = _f32_points(y, "tsne_gradient.y")
+    grad = torch.empty_like(y)
+    rc = lib().ssamd_tsne_iter(_ptr(P), _ptr(y), N, _ptr(ws), float(exaggeration), 0.0, 0.0, None, None, _ptr(grad),
+                               None, 0, _stream())
+    _check(rc, "ssamd_tsne_iter")
+    planes = ws[:6 * N].view(6, N)
+    return planes[0:2].t().contiguous(), planes[2:4].t().contiguous(), planes[4].clone(), grad
+
+
+@torch.no_grad()
+def tsne_kl(P, y):
+    """``ops.reference.tsne_kl`` on the GPU -> a 0-d fp32 tensor."""
+    N, P, ws = _tsne_operands(P, y)
+    y = _f32_points(y, "tsne_kl.y")
+    kl = torch.empty(1, device=y.device, dtype=torch.float32)
+    rc = lib().ssamd_tsne_iter(_ptr(P), _ptr(y), N, _ptr(ws), 1.0, 0.0, 0.0, None, None, None, _ptr(kl), 0, _stream())
+    _check(rc, "ssamd_tsne_iter")
+    return kl[0]
+
+
+@torch.no_grad()
+def tsne_step(P, y, update, gains, exaggeration, momentum, lr):
+    """One iteration of ``ops.reference.tsne``: ``tsne_gradient`` then ``tsne_step`` -> new (y, update, gains)."""
+    N, P, ws = _tsne_operands(P, y)
+    y, update, gains = (_f32_points(t, "tsne_step." + n).clone() for t, n in ((y, "y"), (update, "update"),
+                                                                              (gains, "gains")))
+    rc = lib().ssamd_tsne_iter(_ptr(P), _ptr(y), N, _ptr(ws), float(exaggeration), float(momentum), float(lr),
+                               _ptr(update), _ptr(gains), None, None, 1, _stream())
+    _check(rc, "ssamd_tsne_iter")
+    return y, update, gains
+
+
+@torch.no_grad()
+def tsne(x, perplexity=30.0, n_iter=750, exag_iter=250, early_exaggeration=12.0, init="pca", seed=0, kl_every=50,
+         P=None):
+    """``ops.reference.tsne`` on the GPU: the whole loop is enqueued without a host synchronisation (the exaggeration
+    and momentum of every iteration are known to the host); the KL trace comes back in one copy at the end."""
+    N, _ = ref.tsne_check(x, perplexity)
+    steps, at = ref.tsne_plan(n_iter, exag_iter, early_exaggeration, kl_every)
+    x = _f32_points(x, "tsne.x")
+    if P is None:
+        P = tsne_affinities(x, perplexity)
+    y = ref.tsne_init(x, init, seed).float().contiguous()
+    N, P, ws = _tsne_operands(P, y)
+    lr = float(ref.tsne_learning_rate(N, early_exaggeration))
+    update, gains = torch.zeros_like(y), torch.ones_like(y)
+    trace = torch.empty(len(at), device=x.device, dtype=torch.float32)
+    fn, s, slot = lib().ssamd_tsne_iter, _stream(), 0
+    args = (_ptr(P), _ptr(y), N, _ptr(ws))
+    for ex, mom, rec in steps:
+        kl = None
+        if rec:
+            kl = trace.data_ptr() + 4 * slot
+            slot += 1
+        _check(fn(*args, ex, mom, lr, _ptr(update), _ptr(gains), None, kl, 1, s), "ssamd_tsne_iter")
+    _check(fn(*args, 1.0, 0.0, 0.0, None, None, None, trace.data_ptr() + 4 * slot, 0, s), "ssamd_tsne_iter")
+    return y, trace.tolist()
+
+
+@torch.no_grad()
+def kmeans(x, k, n_iter=100, seed=0, check_every=4):
+    """``ops.reference.kmeans`` on the GPU (fp32) -> (labels int32 [N], centroids [k, D], iterations).  The count of
+    changed labels of every step stays on the device and is read every ``check_every`` steps; a step after the one
+    that changed nothing recomputes the same centroids from the same labels, bit for bit."""
+    N, D = ref.kmeans_check(x, k)
+    if n_iter < 1:
+        raise ValueError("kmeans: n_iter must be at least 1")
+    x = _f32_points(x, "kmeans.x")
+    dev = x.device
+    cent = torch.empty(k, D, device=dev, dtype=torch.float32)
+    labels = torch.full((N,), -1, device=dev, dtype=torch.int32)
+    changed = torch.ones(n_iter, device=dev, dtype=torch.int32)
+    ws = torch.empty(int(lib().ssamd_kmeans_ws(N, D, k)), device=dev, dtype=torch.float32)
+    s = _stream()
+    _check(lib().ssamd_kmeans_init(_ptr(x), N, D, k, int(seed) % N, _ptr(cent), _ptr(ws), s), "ssamd_kmeans_init")
+    for it in range(n_iter):
+        rc = lib().ssamd_kmeans_step(_ptr(x), N, D, k, _ptr(cent), _ptr(labels), changed.data_ptr() + 4 * it, _ptr(ws), s)
+        _check(rc, "ssamd_kmeans_step")
+        if (it + 1) % check_every == 0 or it + 1 == n_iter:
+            seen = changed[:it + 1].tolist()
+            if 0 in seen:
+                return labels, cent, seen.index(0) + 1
+    return labels, cent, n_iter
+
+
 # ------------------------------------------------------------------------ N = 1 heads
 class _HeadFn(torch.autograd.Function):
     """Variance-predictor head Linear(C -> 1) + pad mask (one wave per row)."""

@@ -1051,3 +1051,251 @@ def interp_unvoiced(f0, frames):
         outs.append(torch.where(v, y, g))
     out = torch.cat(outs) if outs else f0.new_zeros(0)
     return out, torch.tensor(counts, dtype=torch.int32, device=f0.device)
+
+
+# ------------------------------------------------------------------------ style map: exact t-SNE and k-means
+TSNE_MAX_N = 16384        # a distance row of the perplexity kernel lives in LDS
+TSNE_ENTROPY_TOL = 1e-5   # scikit-learn's exact method: |H - log perplexity| of a row
+TSNE_BISECT_STEPS = 100
+KMEANS_MAX_K = 64
+KMEANS_MAX_D = 512
+
+
+def tsne_check(x, perplexity):
+    """Argument rules of ``tsne_affinities`` / ``tsne`` (the same on both paths) -> (N, D)."""
+    if x.dim() != 2:
+        raise ValueError(f"tsne: x must be [N, D], got shape {tuple(x.shape)}")
+    N, D = x.shape
+    if N < 7:
+        raise ValueError(f"tsne: x has N = {N} points, at least 7 are needed")
+    if N > TSNE_MAX_N:
+        raise ValueError(f"tsne: x has N = {N} points, more than TSNE_MAX_N = {TSNE_MAX_N}; subsample first")
+    if D < 1:
+        raise ValueError("tsne: x has no columns")
+    if not perplexity >= 2:
+        raise ValueError(f"tsne: perplexity = {perplexity} is below 2")
+    if perplexity > (N - 1) / 3:
+        raise ValueError(f"tsne: perplexity = {perplexity} exceeds (N - 1) / 3 = {(N - 1) / 3:g}")
+    return N, D
+
+
+def pairwise_sqdist(x, chunk_elems=1 << 24):
+    """Squared Euclidean distances [N, N], summed from the differences (never from norms) in row chunks, so that no
+    N x N x D temporary exists."""
+    N, D = x.shape
+    out = x.new_empty(N, N)
+    rows = max(1, min(N, chunk_elems // max(1, N * D)))
+    for r0 in range(0, N, rows):
+        d = x[r0:r0 + rows, None, :] - x[None, :, :]
+        out[r0:r0 + rows] = (d * d).sum(-1)
+    return out
+
+
+def tsne_conditional(x, perplexity):
+    """The row-normalised affinities of t-SNE -> (P_cond [N, N] with a zero diagonal, beta [N] as last evaluated).
+    Per row: the smallest off-diagonal distance is subtracted before the exponential (P is unchanged, the row sum is
+    >= 1 and fp32 stays in range), then beta is bisected as scikit-learn's exact method does it: beta = 1, at most 100
+    steps, a row stops at |H - log perplexity| <= 1e-5 and keeps the P of that evaluation, beta doubles / halves while
+    a bound is infinite and takes the midpoint otherwise."""
+    N, _ = tsne_check(x, perplexity)
+    dt, dev = x.dtype, x.device
+    dist = pairwise_sqdist(x)
+    eye = torch.eye(N, dtype=torch.bool, device=dev)
+    dmin = dist.masked_fill(eye, float("inf")).min(dim=1, keepdim=True).values
+    dist = dist - dmin
+    target = math.log(perplexity)
+    beta = torch.ones(N, 1, dtype=dt, device=dev)
+    lo = torch.full_like(beta, -float("inf"))
+    hi = torch.full_like(beta, float("inf"))
+    active = torch.ones(N, 1, dtype=torch.bool, device=dev)
+    P = torch.zeros_like(dist)
+    beta_used = beta.clone()
+    for _ in range(TSNE_BISECT_STEPS):
+        p = torch.exp(-dist * beta).masked_fill(eye, 0.0)
+        s = p.sum(1, keepdim=True)
+        H = torch.log(s) + beta * (dist * p).sum(1, keepdim=True) / s
+        P = torch.where(active, p / s, P)
+        beta_used = torch.where(active, beta, beta_used)
+        diff = H - target
+        active = active & ~(diff.abs() <= TSNE_ENTROPY_TOL)
+        if not bool(active.any()):
+            break
+        up = active & (diff > 0)   # entropy too high: raise beta
+        dn = active & ~(diff > 0)
+        lo = torch.where(up, beta, lo)
+        hi = torch.where(dn, beta, hi)
+        nb_up = torch.where(torch.isinf(hi), beta * 2, (beta + hi) / 2)
+        nb_dn = torch.where(torch.isinf(lo), beta / 2, (beta + lo) / 2)
+        beta = torch.where(up, nb_up, torch.where(dn, nb_dn, beta))
+    return P, beta_used.reshape(N)
+
+
+def tsne_affinities(x, perplexity):
+    """Joint affinities of exact t-SNE: x [N, D] -> P [N, N] = (P_cond + P_cond^T) / sum, symmetric, zero diagonal,
+    sums to 1 (``tsne_conditional``).  Computes in x's dtype; float64 is the oracle."""
+    pc, _ = tsne_conditional(x, perplexity)
+    s = pc + pc.t()
+    return s / s.sum()
+
+
+def _tsne_w(y):
+    d = y[:, None, :] - y[None, :, :]
+    w = 1.0 / (1.0 + (d * d).sum(-1))
+    return d, w.masked_fill(torch.eye(y.shape[0], dtype=torch.bool, device=y.device), 0.0)
+
+
+def tsne_gradient(P, y, exaggeration=1.0):
+    """Gradient of KL(exaggeration * P || Q) for the Student-t map y [N, 2] -> (attr [N, 2], rep [N, 2], zrow [N],
+    grad [N, 2]): w_ij = 1 / (1 + |y_i - y_j|^2), attr_i = sum_j P_ij w_ij (y_i - y_j), rep_i = sum_j w_ij^2
+    (y_i - y_j), zrow_i = sum_j w_ij, grad = 4 (exaggeration attr - rep / sum zrow)."""
+    d, w = _tsne_w(y)
+    attr = ((P * w).unsqueeze(-1) * d).sum(1)
+    rep = ((w * w).unsqueeze(-1) * d).sum(1)
+    zrow = w.sum(1)
+    grad = 4.0 * (exaggeration * attr - rep / zrow.sum())
+    return attr, rep, zrow, grad
+
+
+def tsne_kl(P, y):
+    """KL(P || Q) of the map: sum_{P > 0} P (log P - log w) + log Z."""
+    _, w = _tsne_w(y)
+    pos = P > 0
+    eye = torch.eye(y.shape[0], dtype=torch.bool, device=y.device)
+    lw = torch.log(torch.where(eye, torch.ones_like(w), w))
+    lp = torch.log(torch.where(pos, P, torch.ones_like(P)))
+    return (torch.where(pos, P * (lp - lw), torch.zeros_like(P))).sum() + torch.log(w.sum())
+
+
+def tsne_step(grad, y, update, gains, momentum, lr):
+    """One descent step with per-element gains -> (y, update, gains): gains + 0.2 where update and gradient disagree
+    in sign (update * grad < 0), x 0.8 otherwise, floor 0.01; update = momentum update - lr gains grad."""
+    inc = update * grad < 0
+    gains = torch.where(inc, gains + 0.2, gains * 0.8).clamp(min=0.01)
+    update = momentum * update - lr * (gains * grad)
+    return y + update, update, gains
+
+
+def tsne_learning_rate(N, early_exaggeration=12.0):
+    return max(N / early_exaggeration / 4.0, 50.0)
+
+
+def tsne_init(x, init="pca", seed=0):
+    """The start of the map, [N, 2] in x's dtype on x's device, made on the host so that every path starts from the
+    same y0.  "pca": the top two eigenvectors of the D x D covariance in float64, each sign fixed so that the entry of
+    largest magnitude is positive, scaled so that the first component has standard deviation 1e-4.  "random":
+    N(0, 1e-4^2) from a seeded CPU generator.  A tensor is taken as it is."""
+    N = x.shape[0]
+    if isinstance(init, torch.Tensor):
+        if tuple(init.shape) != (N, 2):
+            raise ValueError(f"tsne: init must be [{N}, 2], got shape {tuple(init.shape)}")
+        return init.detach().to(device=x.device, dtype=x.dtype).clone()
+    if init == "random":
+        g = torch.Generator().manual_seed(int(seed))
+        y = torch.randn(N, 2, generator=g, dtype=torch.float64) * 1e-4
+    elif init == "pca":
+        xc = x.detach().to("cpu", torch.float64)
+        xc = xc - xc.mean(0, keepdim=True)
+        cov = xc.t() @ xc / max(N - 1, 1)
+        _, vec = torch.linalg.eigh(cov)
+        comp = vec[:, -2:].flip(1) if vec.shape[1] >= 2 else torch.cat([vec, torch.zeros_like(vec)], 1)
+        big = comp.abs().argmax(0)
+        sign = torch.sign(comp[big, torch.arange(comp.shape[1])])
+        comp = comp * torch.where(sign == 0, torch.ones_like(sign), sign)
+        y = xc @ comp
+        sd = y[:, 0].std()
+        y = y / sd * 1e-4 if sd > 0 else y
+    else:
+        raise ValueError(f"tsne: init must be 'pca', 'random' or a tensor, got {init!r}")
+    return y.to(device=x.device, dtype=x.dtype)
+
+
+def tsne_plan(n_iter, exag_iter, early_exaggeration, kl_every):
+    """Per iteration (exaggeration, momentum, record KL before this step?) and the iteration counts the KL trace
+    reports: every ``kl_every`` updates and after the last one."""
+    if n_iter < 1 or exag_iter < 0 or kl_every < 1:
+        raise ValueError("tsne: n_iter >= 1, exag_iter >= 0 and kl_every >= 1 are needed")
+    steps = [(float(early_exaggeration) if it < exag_iter else 1.0, 0.5 if it < exag_iter else 0.8,
+              it > 0 and it % kl_every == 0) for it in range(n_iter)]
+    at = [it for it in range(kl_every, n_iter, kl_every)] + [n_iter]
+    return steps, at
+
+
+def tsne(x, perplexity=30.0, n_iter=750, exag_iter=250, early_exaggeration=12.0, init="pca", seed=0, kl_every=50,
+         P=None):
+    """Exact t-SNE of x [N, D] -> (y [N, 2], kl_trace): gradient descent with momentum 0.5 during the ``exag_iter``
+    exaggerated iterations and 0.8 after, learning rate max(N / early_exaggeration / 4, 50), per-element gains, a
+    fixed iteration count.  kl_trace[i] is KL(P || Q) (never exaggerated) after ``tsne_plan``'s i-th count of updates;
+    its last entry is the final map's.  Computes in x's dtype."""
+    N, _ = tsne_check(x, perplexity)
+    steps, _ = tsne_plan(n_iter, exag_iter, early_exaggeration, kl_every)
+    if P is None:
+        P = tsne_affinities(x, perplexity)
+    y = tsne_init(x, init, seed)
+    lr = tsne_learning_rate(N, early_exaggeration)
+    update, gains = torch.zeros_like(y), torch.ones_like(y)
+    trace = []
+    for ex, mom, rec in steps:
+        if rec:
+            trace.append(float(tsne_kl(P, y)))
+        grad = tsne_gradient(P, y, ex)[3]
+        y, update, gains = tsne_step(grad, y, update, gains, mom, lr)
+    trace.append(float(tsne_kl(P, y)))
+    return y, trace
+
+
+def kmeans_check(x, k):
+    if x.dim() != 2:
+        raise ValueError(f"kmeans: x must be [N, D], got shape {tuple(x.shape)}")
+    N, D = x.shape
+    if not 1 <= k <= KMEANS_MAX_K:
+        raise ValueError(f"kmeans: k = {k} is outside 1 .. {KMEANS_MAX_K}")
+    if k > N:
+        raise ValueError(f"kmeans: k = {k} exceeds N = {N}")
+    if not 1 <= D <= KMEANS_MAX_D:
+        raise ValueError(f"kmeans: D = {D} is outside 1 .. {KMEANS_MAX_D}")
+    return N, D
+
+
+def _sqdist_ordered(x, c):
+    """[N, k] squared distances, summed over the columns in increasing order, every product and sum rounded on its
+    own: what one accumulator per pair gives."""
+    acc = x.new_zeros(x.shape[0], c.shape[0])
+    for d in range(x.shape[1]):
+        df = x[:, d:d + 1] - c[None, :, d]
+        acc = acc + df * df
+    return acc
+
+
+def kmeans(x, k, n_iter=100, seed=0):
+    """Lloyd's k-means with a farthest-point start -> (labels int32 [N], centroids [k, D], iterations).  The first
+    centre is point ``seed % N``; each next one is the point farthest from its nearest chosen centre (lowest index on
+    ties).  A step assigns every point to its nearest centroid (lowest index on ties; distances summed from the
+    differences in column order) and sets each centroid to sum / count of its points in index order; an empty cluster
+    keeps its centroid.  Stops when no label changes, or after ``n_iter`` steps."""
+    N, D = kmeans_check(x, k)
+    if n_iter < 1:
+        raise ValueError("kmeans: n_iter must be at least 1")
+    idx = int(seed) % N
+    cent = x.new_empty(k, D)
+    mind = x.new_full((N,), float("inf"))
+    for c in range(k):
+        cent[c] = x[idx]
+        mind = torch.minimum(mind, _sqdist_ordered(x, cent[c:c + 1])[:, 0])
+        idx = int(torch.nonzero(mind == mind.max())[0])
+    labels = torch.full((N,), -1, dtype=torch.int64, device=x.device)
+    iterations = 0
+    for it in range(n_iter):
+        dist = _sqdist_ordered(x, cent)
+        best = dist.min(1, keepdim=True).values
+        ids = torch.arange(k, device=x.device).expand(N, k)
+        new = torch.where(dist == best, ids, torch.full_like(ids, k)).min(1).values  # first index of the minimum
+        changed = int((new != labels).sum())
+        labels = new
+        iterations = it + 1
+        if changed == 0:
+            break
+        sums = x.new_zeros(k, D).index_add_(0, labels, x)
+        cnt = torch.bincount(labels, minlength=k)
+        has = cnt > 0
+        cent = torch.where(has[:, None], sums / cnt.clamp(min=1).to(x.dtype)[:, None], cent)
+    return labels.to(torch.int32), cent, iterations

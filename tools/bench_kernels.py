@@ -4,12 +4,14 @@
 Reports achieved TFLOP/s (GEMM-shaped) or GB/s (memory-bound) per kernel, and
 the hipBLASLt number for the plain-GEMM equivalent (torch.matmul) as a yardstick.
 Usage (GPU box): python tools/bench_kernels.py [--rows 160000] [--iters 20] | --griffin-lim | --dtw | --align | --yin
-       | --pyin | --k256 | --prosody | --features
+       | --pyin | --k256 | --prosody | --tsne | --features
 """
 import argparse
+import functools
 import json
 import math
 import os
+import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -635,20 +637,24 @@ def prosody_workload():
             torch.from_numpy(rng.uniform(1, 60, ry)).float(), torch.from_numpy(rng.standard_normal(dur.shape)).float())
 
 
-def _kernel_resources(src, name):
-    """Register / scratch / LDS figures of kernel ``name`` from a compile of ``src`` for gfx950 (remarks of
-    ``-Rpass-analysis=kernel-resource-usage``)."""
-    import subprocess
-
+@functools.lru_cache(maxsize=None)
+def _resource_remarks(src):
+    """The compiler's remarks for one compile of ``src`` (a file with many kernels is compiled once)."""
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
     cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-c", os.path.join(csrc, src), "--offload-arch=gfx950",
            "-std=c++17", "-O3", "-I", csrc, "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull]
+    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600).stdout
+
+
+def _kernel_resources(src, name):
+    """Register / scratch / LDS figures of kernel ``name`` from a compile of ``src`` for gfx950 (remarks of
+    ``-Rpass-analysis=kernel-resource-usage``)."""
     try:
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+        remarks = _resource_remarks(src)
     except (OSError, subprocess.TimeoutExpired) as e:
         return [f"compile figures not available: {e}"]
     keep, on = [], False
-    for line in r.stdout.splitlines():
+    for line in remarks.splitlines():
         if "remark:" not in line:
             continue
         text = line.split("remark:", 1)[1].split("[-Rpass")[0].strip()
@@ -658,6 +664,93 @@ def _kernel_resources(src, name):
                                          "Occupancy [waves/SIMD]", "LDS Size [bytes/block]"):
             keep.append(text)
     return keep or ["compile figures not available: no remarks for " + name]
+
+
+STYLEMAP_KERNELS = ("tsne_pairdist_kernel", "tsne_perplexity_kernel", "tsne_planesum_kernel", "tsne_symmetrise_kernel",
+                    "tsne_grad_kernel", "tsne_update_kernel", "kmeans_far_kernel", "kmeans_pick_kernel",
+                    "kmeans_assign_kernel", "kmeans_finish_kernel")
+
+
+def bench_tsne(out_path, sizes=(1024, 4096, 13100), dim=512, n_iter=750, rounds=3):
+    """The style-map ops (csrc/k_stylemap.hip) against the torch references of ``ops/reference.py`` on the same GPU
+    tensors (float32), arms alternating in one process, wall time between device synchronisations: affinities, one
+    gradient evaluation, the whole descent, k-means (k = 10).  Where the reference's descent would run for minutes it is
+    timed over 20 iterations and scaled, and the row says so.  scikit-learn's TSNE on the host, where it imports:
+    ``exact`` at N = 1024, ``barnes_hut`` above."""
+    import time
+
+    from speakingstyle_amd import ops
+    from speakingstyle_amd.ops import reference as ref
+
+    dev = torch.device("cuda")
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    def row(name, arm, v, note=""):
+        v = sorted(v)
+        return f"{name:34s} {arm:>24s} {v[len(v) // 2]:12.3f} {v[0]:12.3f} {v[-1]:12.3f}  {note}"
+
+    lines = [f"Style map: exact t-SNE and k-means, fp32, D = {dim}, {torch.cuda.get_device_name(0)}",
+             "kernels of csrc/k_stylemap.hip, compiled for gfx950:"]
+    for k in STYLEMAP_KERNELS:
+        lines.append(f"  {k}: " + "; ".join(_kernel_resources("k_stylemap.hip", k)))
+    lines += [f"{rounds} alternating rounds per arm after 1 warm-up round (the {n_iter}-iteration rows: 1 round); wall "
+              "time per call between device syncs (ms)", "",
+              f"{'workload':34s} {'arm':>24s} {'median':>12s} {'min':>12s} {'max':>12s}"]
+    for n in sizes:
+        g = torch.Generator().manual_seed(n)
+        centres = torch.randn(10, dim, generator=g) * 3.0
+        x = (centres[torch.randint(0, 10, (n,), generator=g)] + torch.randn(n, dim, generator=g)).to(dev)
+        perp = 30.0
+        P = ops.tsne_affinities(x, perp)
+        y = (torch.randn(n, 2, generator=g) * 5.0).to(dev)
+        arms = [("affinities", lambda: ops.tsne_affinities(x, perp), lambda: ref.tsne_affinities(x, perp)),
+                ("one gradient", lambda: ops.tsne_gradient(P, y, 1.0), lambda: ref.tsne_gradient(P, y, 1.0)),
+                ("k-means k=10", lambda: ops.kmeans(x, 10), lambda: ref.kmeans(x, 10))]
+        for what, hip_fn, ref_fn in arms:
+            t = {"hip": [], "torch reference": []}
+            for r in range(rounds + 1):
+                for arm, fn in (("hip", hip_fn), ("torch reference", ref_fn)):
+                    ms = wall(fn)
+                    if r >= 1:
+                        t[arm].append(ms)
+            name = f"N = {n}: {what}"
+            for arm, v in t.items():
+                lines.append(row(name, arm, v))
+            h, q = sorted(t["hip"]), sorted(t["torch reference"])
+            lines.append(f"{'':34s} {'torch / hip (medians)':>24s} {q[len(q) // 2] / h[len(h) // 2]:12.1f}")
+            print(lines[-3] + "\n" + lines[-2] + "\n" + lines[-1], flush=True)
+        name = f"N = {n}: {n_iter} iterations"
+        wall(lambda: hip.tsne(x, perp, 20, 10, P=P))
+        out = {}
+        lines.append(row(name, "hip", [wall(lambda: out.update(r=hip.tsne(x, perp, n_iter, 250, P=P)))],
+                     f"final KL {out['r'][1][-1]:.4f}"))
+        short = n_iter if n <= 4096 else 20
+        wall(lambda: ref.tsne(x, perp, 3, 1, P=P))
+        ms = wall(lambda: out.update(q=ref.tsne(x, perp, short, min(250, short // 2), P=P)))
+        note = f"final KL {out['q'][1][-1]:.4f}" if short == n_iter else f"{short} iterations timed, scaled to {n_iter}"
+        lines.append(row(name, "torch reference", [ms * n_iter / short], note))
+        print(lines[-2] + "\n" + lines[-1], flush=True)
+        try:
+            from sklearn.manifold import TSNE
+        except ImportError:
+            lines.append(f"{name:34s} {'scikit-learn (host)':>24s} not installed")
+            continue
+        method = "exact" if n <= 1024 else "barnes_hut"
+        xs = x.cpu().numpy()
+        t0 = time.perf_counter()
+        sk = TSNE(perplexity=perp, max_iter=n_iter, method=method, init="pca", random_state=0,
+                  n_iter_without_progress=n_iter).fit(xs)
+        lines.append(row(name, f"scikit-learn {method}", [1e3 * (time.perf_counter() - t0)],
+                         f"host, {os.cpu_count()} logical CPUs seen; KL {sk.kl_divergence_:.4f}"))
+        print(lines[-1], flush=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
 
 
 def bench_prosody(out_path, rounds=5):
@@ -991,6 +1084,10 @@ def main():
     ap.add_argument("--prosody", action="store_true",
                     help="only the prosody-transfer arm: the kernel vs the torch reference on the GPU, and "
                          "synthesize_like vs plain synthesis for one utterance")
+    ap.add_argument("--tsne", action="store_true",
+                    help="only the style-map arm: t-SNE affinities, gradient, 750 iterations and k-means at N = 1024, "
+                         "4096, 13100 (D = 512), kernels vs the torch reference on the GPU, scikit-learn on the host "
+                         "(profiles/style_map.txt)")
     ap.add_argument("--features", action="store_true",
                     help="only the feature front-end: the packed ops.frame_features launch vs the per-utterance loop over "
                          "hip.logmel and torch.stft + matmul (profiles/features.txt), then Preprocessor end to end, host "
@@ -1009,6 +1106,8 @@ def main():
         return bench_preprocess(os.path.join(os.path.dirname(os.path.abspath(out)), "preprocess_gpu.txt"))
     if args.prosody:
         return bench_prosody(args.out or os.path.join(prof, "prosody_transfer.txt"))
+    if args.tsne:
+        return bench_tsne(args.out or os.path.join(prof, "style_map.txt"))
     if args.k256:
         return bench_k256(args.out or os.path.join(prof, "k256_shapes.txt"), iters=args.iters)
     if args.pyin:
