@@ -130,7 +130,8 @@ def build_selftest(name, headers):
 
 # name -> the headers its self-test covers (tests/test_*_host.py)
 SELFTESTS = {"attn_blockmap": ["attn_blockmap.h"], "gl_frames": ["gl_frames.h"], "dtw_index": ["dtw_index.h"],
-             "k256_split": ["k256_split.h"], "gemm_route": ["gemm_route.h", "k256_split.h"]}
+             "k256_split": ["k256_split.h"], "gemm_route": ["gemm_route.h", "k256_split.h"],
+             "istft_index": ["istft_index.h"]}
 
 
 def build_blockmap_selftest():
@@ -147,6 +148,10 @@ def build_dtw_selftest():
 
 def build_k256_selftest():
     return build_selftest("k256_split", SELFTESTS["k256_split"])
+
+
+def build_istft_selftest():
+    return build_selftest("istft_index", SELFTESTS["istft_index"])
 
 
 if __name__ == "__main__":

@@ -19,6 +19,12 @@ output rows are the interleaved phases (``convT_as_conv3``), activations / bias 
 residual / MRF mean sit in GEMM epilogues, the C <= 128 ResBlocks are single fused
 layer kernels.  The CPU path (tests) uses the polyphase decomposition.  Training runs in PyTorch NCL
 layout with autograd (vocoder training is not a headline config).
+
+With ``gen_istft_n_fft`` / ``gen_istft_hop_size`` in the config (``config/hifigan/config_istft.json``, the key
+names of public iSTFTNet configs) the generator is iSTFTNet (Kaneko et al., ICASSP 2022): fewer upsampling
+stages, ``conv_post`` predicts n_fft/2 + 1 log-magnitudes and phases per frame and an inverse STFT with
+overlap-add produces the samples (``ops.istft_head``, ``csrc/k_istft.hip`` at n_fft 16 / hop 4).  Module names
+are unchanged; without the keys every path is HiFi-GAN as before.
 """
 from __future__ import annotations
 
@@ -264,9 +270,31 @@ class Generator(nn.Module):
             ch = c0 // 2 ** (i + 1)
             for k, d in zip(h.resblock_kernel_sizes, h.resblock_dilation_sizes):
                 self.resblocks.append(ResBlock1(ch, k, d))
-        self.conv_post = weight_norm(nn.Conv1d(ch, 1, 7, 1, padding=3))
+        # iSTFTNet (Kaneko et al. 2022): ``gen_istft_n_fft`` / ``gen_istft_hop_size`` make conv_post predict
+        # n_fft/2 + 1 log-magnitudes and as many phases per frame; an inverse STFT produces the samples
+        self.istft = _istft_keys(h)
+        self.conv_post = weight_norm(nn.Conv1d(ch, 1 if self.istft is None else self.istft[0] + 2, 7, 1, padding=3))
         self.ups.apply(_init)
         self.conv_post.apply(_init)
+
+    @property
+    def hop(self) -> int:
+        """Samples per mel frame: the product of the upsampling rates, times the iSTFT hop of an iSTFTNet head."""
+        hop = 1
+        for u in self.h.upsample_rates:
+            hop *= u
+        return hop if self.istft is None else hop * self.istft[1]
+
+    def _istft_ncl(self, a, w=None, b=None):
+        """iSTFTNet head on the activated last stage a [B, C, T] (fp32, autograd): one reflected column on the
+        left, conv_post (its module, or the given effective weight), exp / sin, ``torch.istft`` -> [B, 1, T * hop]."""
+        N, H = self.istft
+        p = F.pad(a, (1, 0), mode="reflect")
+        z = self.conv_post(p) if w is None else F.conv1d(p, w, b, padding=3)
+        nb = N // 2 + 1
+        spec = torch.polar(torch.exp(z[:, :nb]), torch.sin(z[:, nb:]))
+        win = torch.hann_window(N, periodic=True, device=z.device, dtype=z.dtype)
+        return torch.istft(spec, N, H, N, window=win, center=True).unsqueeze(1)
 
     # ------------------------------------------------------------------ training (NCL)
     def forward(self, x):
@@ -280,6 +308,8 @@ class Generator(nn.Module):
                 y = self.resblocks[i * self.num_kernels + j](x)
                 xs = y if xs is None else xs + y
             x = xs / self.num_kernels
+        if self.istft is not None:
+            return self._istft_ncl(F.leaky_relu(x))  # no tanh: the waveform is the inverse STFT itself
         x = self.conv_post(F.leaky_relu(x))  # default slope 0.01 (reference quirk, D16 preserved)
         return torch.tanh(x)
 
@@ -297,7 +327,9 @@ class Generator(nn.Module):
         [B, T, s*Cout] output reshapes to the interleaved [B, T*s, Cout]; LeakyReLU / residual /
         MRF mean are torch elementwise ops; conv_post (one output channel, not MFMA-shaped) is a
         torch conv on the fp32 activation.  Same function as ``forward`` (reference
-        ``hifigan/models.py:124-165``), returns [B, 1, T*hop] fp32."""
+        ``hifigan/models.py:124-165``), returns [B, 1, T*hop] fp32.  An iSTFTNet head keeps this trunk and runs
+        ``F.conv1d`` + ``torch.istft`` on the fp32 activation through autograd: the head kernel
+        (``csrc/k_istft.hip``) is inference-only, a HIP backward for it does not exist."""
         B = x.shape[0]
         h = x.transpose(1, 2).to(torch.bfloat16).contiguous()
         glue = _glue(h)
@@ -319,6 +351,8 @@ class Generator(nn.Module):
                     xs = xs + r
                 h = xs / nk
         cp = self.conv_post
+        if self.istft is not None:
+            return self._istft_ncl(F.leaky_relu(h.float(), 0.01).transpose(1, 2), _wn(cp), cp.bias)
         if glue is not _TorchGlue and cp.out_channels == 1:
             # lrelu(0.01) -> conv (Cout = 1) -> tanh on the HIP sconv kernel, fp32 [B, T, 1] -> [B, 1, T]
             return glue.conv_post_tanh(h, _wn(cp), cp.bias, cp.padding[0]).reshape(B, 1, -1)
@@ -333,6 +367,11 @@ class Generator(nn.Module):
         stage's rate and converting across each transposed conv (input index (o + pad - k) / s)."""
         nk = self.num_kernels
         r = (self.conv_post.kernel_size[0] - 1) // 2
+        if self.istft is not None:
+            # a sample reads the frames floor(n / hop) - halo .. + halo + 1, a frame the padded positions within 3,
+            # and position j is row j - 1: conv 3 + frames + the pad shift (6 rows at n_fft 16 / hop 4)
+            N, H = self.istft
+            r += (N // 2 - 1) // H + 2
         for i in reversed(range(self.num_upsamples)):
             blocks = [self.resblocks[i * nk + j] for j in range(nk)]
             r += max(sum(d * (b.kernel_size - 1) // 2 + (b.kernel_size - 1) // 2 for d in b.dilation) for b in blocks)
@@ -392,18 +431,13 @@ class Generator(nn.Module):
         utterance exactly as if alone, no padded rows; its samples past ``lengths[b] * hop`` are zero."""
         if (lengths is not None and _PACKED[0] and mel_cl.is_cuda and ops.use_hip(mel_cl)
                 and mel_cl.dtype in (torch.float32, torch.bfloat16) and self.packable()):
-            hop = 1
-            for u in self.h.upsample_rates:
-                hop *= u
-            return self.infer_packed(mel_cl, lengths, int16_scale, width=mel_cl.shape[1] * hop)
+            return self.infer_packed(mel_cl, lengths, int16_scale, width=mel_cl.shape[1] * self.hop)
         if lengths is not None and mel_cl.shape[0] > 1:
             B, T, _ = mel_cl.shape
             groups = self.length_buckets([int(v) for v in lengths], T, self.receptive_radius(), max_buckets,
                                          bucket_cost)
             if len(groups) > 1 or groups[0][1] < T:
-                hop = 1
-                for u in self.h.upsample_rates:
-                    hop *= u
+                hop = self.hop
                 out = None
                 for idx, Tb in groups:
                     sel = torch.as_tensor(idx, device=mel_cl.device)
@@ -426,6 +460,8 @@ class Generator(nn.Module):
                 xs = blk.forward_cl(x, acc=xs, out_scale=(1.0 / self.num_kernels) if last else 1.0, x_act=x_act)
             x = xs
         w = _w(self.conv_post)
+        if self.istft is not None:
+            return ops.istft_head(x, w, self.conv_post.bias, *self.istft, int16_scale=int16_scale)
         y = torch.tanh(ref_conv_post(_lrelu(x, 0.01), w, self.conv_post.bias)).squeeze(-1)
         if int16_scale is not None:
             y = (y * int16_scale).clamp(-32768, 32767).to(torch.int16)
@@ -490,6 +526,8 @@ class Generator(nn.Module):
                                     post_lrelu=post and last)
             x = xs
         w = _w(self.conv_post)  # [1, C, 7]: N = 1 output -> VALU kernel (lrelu + conv + tanh [+ int16] fused)
+        if self.istft is not None:  # [n_fft + 2, C, 7]: the head kernel at n_fft 16 / hop 4, else the torch head
+            return ops.istft_head(x, w, self.conv_post.bias, *self.istft, int16_scale=int16_scale)
         if x.shape[-1] in (8, 32):
             return hip.conv_post(x, w, self.conv_post.bias, 0.01, int16_scale)
         y = torch.tanh(ref_conv_post(_lrelu(x, 0.01), w, self.conv_post.bias)).squeeze(-1)
@@ -499,9 +537,14 @@ class Generator(nn.Module):
 
     # ------------------------------------------------------------------ packed (length-exact) inference
     def packable(self) -> bool:
-        """Every upsampler has the 3-tap form and conv_post the VALU kernel: ``infer_packed`` applies."""
+        """Every upsampler has the 3-tap form and conv_post the VALU kernel (an iSTFTNet head: its kernel is
+        built for this width and iSTFT size): ``infer_packed`` applies."""
         c_last = self.h.upsample_initial_channel // 2 ** self.num_upsamples
-        return c_last in (8, 32) and all(_conv3_form(up.kernel_size[0], up.stride[0], up.padding[0])
+        if self.istft is not None:
+            post = c_last % 64 == 0 and ops._hip().istft_head_has(c_last, *self.istft)
+        else:
+            post = c_last in (8, 32)
+        return post and all(_conv3_form(up.kernel_size[0], up.stride[0], up.padding[0])
                                          for up in self.ups)
 
     def _packed_geoms(self, lens):
@@ -522,7 +565,7 @@ class Generator(nn.Module):
             for blk in blocks:
                 geoms.extend(blk.packed_tiles(cout, rate, lens))
         c_last = self.h.upsample_initial_channel // 2 ** self.num_upsamples
-        geoms.append((rate, hip.voc_tile_rows("post", c_last)))
+        geoms.append((rate, hip.voc_tile_rows("post" if self.istft is None else "istft", c_last)))
         return geoms
 
     def cap_pack(self, nreal: int, Rcap: int, Mcap: int, device):
@@ -551,9 +594,7 @@ class Generator(nn.Module):
         hip = ops._hip()
         dev = mel.device
         rows_in = mel.dim() == 2  # already packed [R, n_mel] rows in ``lengths`` order (FastSpeech2.infer_packed)
-        hop = 1
-        for u in self.h.upsample_rates:
-            hop *= u
+        hop = self.hop
         nk = self.num_kernels
         if cap is not None:
             assert rows_in and mel.shape[0] == cap.R and width is None, "infer_packed: capacity rows"
@@ -604,6 +645,8 @@ class Generator(nn.Module):
                 xs = blk.forward_packed(y, vp, rate, acc=xs, out_scale=(1.0 / nk) if last else 1.0, x_act=x_act,
                                         post_lrelu=post and last)
             x = xs
+        if self.istft is not None:
+            return hip.istft_head_packed(x, vp, rate, _w(self.conv_post), self.conv_post.bias, out, int16_scale)
         return hip.conv_post_packed(x, vp, rate, _w(self.conv_post), self.conv_post.bias, out, 0.01, int16_scale)
 
     def fold_weight_norm(self):
@@ -627,6 +670,25 @@ _PACKED = [True]
 _CONV3_SQ = [True]
 # the other upsamplers' 3-tap GEMM skips each 256-column tile's all-zero tap (ConvGeom::ksplit in csrc/k_gemm.hip)
 _CONVT_KSPLIT = [True]
+
+
+def _istft_keys(h):
+    """(n_fft, hop) of an iSTFTNet head from the config keys public iSTFTNet configs use, None for HiFi-GAN."""
+    nf, hs = h.get("gen_istft_n_fft"), h.get("gen_istft_hop_size")
+    if nf is None and hs is None:
+        return None
+    if nf is None or hs is None:
+        raise ValueError("iSTFTNet needs both gen_istft_n_fft and gen_istft_hop_size")
+    nf, hs = int(nf), int(hs)
+    if nf < 2 or nf % 2 or hs < 1 or hs > nf:
+        raise ValueError(f"gen_istft_n_fft {nf} / gen_istft_hop_size {hs}: an even n_fft and 1 <= hop <= n_fft")
+    up = 1
+    for u in h["upsample_rates"]:
+        up *= int(u)
+    if "hop_size" in h and up * hs != int(h["hop_size"]):
+        raise ValueError(f"prod(upsample_rates) * gen_istft_hop_size = {up} * {hs} = {up * hs} does not equal "
+                         f"hop_size = {h['hop_size']}")
+    return nf, hs
 
 
 def ref_conv_post(x, w, b):

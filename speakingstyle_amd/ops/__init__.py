@@ -402,6 +402,24 @@ def istft(spec, n_fft, hop, window, lengths=None, width=None):
     return ref.istft(spec, n_fft, hop, window, lengths, width)
 
 
+def istft_head_fused(x, n_fft: int, hop: int) -> bool:
+    """Whether ``istft_head`` of x runs on the HIP kernel (bf16 rows on the GPU, a geometry it is built for)."""
+    return (use_hip(x) and x.dtype == torch.bfloat16 and x.shape[-1] % 64 == 0
+            and _hip().istft_head_has(x.shape[-1], n_fft, hop))
+
+
+def istft_head(x, w, b, n_fft, hop, int16_scale=None, slope=0.01):
+    """iSTFTNet head on channel-last last-stage rows x [B, T, C] -> wav [B, hop * T] (int16 = (wav *
+    int16_scale).clamp.to(int16)); see ``ops.reference.istft_head``.  bf16 rows on the GPU at n_fft 16 / hop 4 run
+    one HIP kernel (``csrc/k_istft.hip``); every other size is the torch reference head in fp32."""
+    if istft_head_fused(x, n_fft, hop):
+        return _hip().istft_head(x, w, b, int16_scale, slope)
+    y = ref.istft_head(x.float(), w.float(), None if b is None else b.float(), n_fft, hop, slope)
+    if int16_scale is not None:
+        y = (y * int16_scale).clamp(-32768, 32767).to(torch.int16)
+    return y
+
+
 def griffin_lim(x, n_fft, hop, window, n_iters, momentum=0.99, init_phase=None, seed=0, lengths=None,
                 int16_scale=None, mel_pinv=None, width=None, return_mag=False):
     """Griffin-Lim phase reconstruction of magnitude rows (log-mel rows with ``mel_pinv``); see

@@ -2580,12 +2580,14 @@ def set_resblock_tall(v: int):
 
 def voc_tile_rows(kind, C: int, K: int = 0, dil=(0, 0, 0)) -> int:
     """Tile height of a tiled vocoder kernel (0 resblock_layer (the global variant), 1 resblock_fused, 2 conv3_sq,
-    3 / 4 the tall / 128-row per-layer tile, "post" conv_post)."""
+    3 / 4 the tall / 128-row per-layer tile, "post" conv_post, "istft" the iSTFTNet head)."""
     key = (kind, C, K, tuple(dil))
     v = _TILE_ROWS.get(key)
     if v is None:
         if kind == "post":
             v = int(lib().ssamd_conv_post_tile_rows())
+        elif kind == "istft":
+            v = int(lib().ssamd_istft_head_tile_rows())
         else:
             d0, d1, d2 = (int(x) for x in dil)
             v = int(lib().ssamd_voc_tile_rows(int(kind), int(C), int(K), d0, d1, d2))
@@ -3593,6 +3595,72 @@ def conv_post(x, w, b, slope=0.01, int16_scale=None):
         rc = lib().ssamd_conv_post(_ptr(xc), _ptr(wf), _ptr(bf), B, T, C, float(slope), float(int16_scale), None,
                                    _ptr(out), _stream())
     _check(rc, "ssamd_conv_post")
+    return out
+
+
+# ------------------------------------------------------------------------ iSTFTNet head
+_SIGS.update({"ssamd_istft_head": [P, P, P, I, I, I, I, I, F, F, P, P, P],
+              "ssamd_istft_head_pk": [P, P, P, P, I, I, I, I, F, F, P, P, L_, P],
+              "ssamd_istft_head_tile_rows": [],
+              "ssamd_istft_head_has": [I, I, I]})
+
+
+def istft_head_has(C: int, n_fft: int = 16, hop: int = 4) -> bool:
+    """Whether ``istft_head_kernel`` (csrc/k_istft.hip) is instantiated for this geometry."""
+    return bool(lib().ssamd_istft_head_has(int(C), int(n_fft), int(hop)))
+
+
+def _istft_head_operands(x, w, b, what):
+    C = x.shape[-1]
+    n_fft = w.shape[0] - 2
+    if w.dim() != 3 or w.shape[1] != C or w.shape[2] != 7 or b is None or b.numel() != w.shape[0]:
+        raise ValueError(f"{what}: weight {tuple(w.shape)} / bias for C = {C}")
+    if not istft_head_has(C, n_fft, 4):
+        raise ValueError(f"{what}: no HIP kernel for C = {C}, n_fft = {n_fft} (hop 4)")
+    _need(x, torch.bfloat16, what + ".x")
+    # the bf16 [n_fft + 2][7][C] operand image, through the weight-image cache (version and weight generation)
+    return weight_fwd(w), b.detach().reshape(-1).float().contiguous()
+
+
+def istft_head(x, w, b, int16_scale=None, slope=0.01):
+    """iSTFTNet head (``ops.reference.istft_head``, n_fft 16 / hop 4) on channel-last x [B, T, C] bf16 -> [B, 4 T]
+    fp32, or int16 (x int16_scale, clamped) when ``int16_scale`` is given.  T >= 2."""
+    B, T, C = x.shape
+    if T < 2:
+        raise ValueError("istft_head: the reflection pad needs at least 2 rows per utterance")
+    xc = x.contiguous()
+    wi, bf = _istft_head_operands(xc, w, b, "istft_head")
+    if int16_scale is None:
+        out = torch.empty(B, 4 * T, device=x.device, dtype=torch.float32)
+        rc = lib().ssamd_istft_head(_ptr(xc), _ptr(wi), _ptr(bf), B, T, C, 16, 4, float(slope), 1.0, _ptr(out), None,
+                                    _stream())
+    else:
+        out = torch.empty(B, 4 * T, device=x.device, dtype=torch.int16)
+        rc = lib().ssamd_istft_head(_ptr(xc), _ptr(wi), _ptr(bf), B, T, C, 16, 4, float(slope), float(int16_scale),
+                                    None, _ptr(out), _stream())
+    _check(rc, "ssamd_istft_head")
+    return out
+
+
+def istft_head_packed(x, vp, rate, w, b, out, int16_scale=None, slope=0.01):
+    """``istft_head`` on packed rows x [R*rate, C] into out [B, W] (sample n of sequence u at out[u, n]; the caller
+    zero-fills out): every utterance exactly as if alone."""
+    Rr, C = x.shape
+    wi, bf = _istft_head_operands(x, w, b, "istft_head_packed")
+    tt, n = vp.tiles(rate, voc_tile_rows("istft", C))
+    longest = getattr(vp, "M", None)  # a capacity pack's sequences are bounded by its Mcap, not by ``lens``
+    longest = int(vp.lens.max()) if longest is None else longest
+    assert out.shape[0] == vp.B and out.shape[1] >= longest * rate * 4 and out.stride(1) == 1, \
+        "istft_head_packed: output shape"
+    if int16_scale is None:
+        assert out.dtype == torch.float32
+        rc = lib().ssamd_istft_head_pk(_ptr(x), _ptr(wi), _ptr(bf), _ptr(tt), n, C, 16, 4, float(slope), 1.0,
+                                       _ptr(out), None, out.stride(0), _stream())
+    else:
+        assert out.dtype == torch.int16
+        rc = lib().ssamd_istft_head_pk(_ptr(x), _ptr(wi), _ptr(bf), _ptr(tt), n, C, 16, 4, float(slope),
+                                       float(int16_scale), None, _ptr(out), out.stride(0), _stream())
+    _check(rc, "ssamd_istft_head_pk")
     return out
 
 

@@ -1299,3 +1299,53 @@ def kmeans(x, k, n_iter=100, seed=0):
         has = cnt > 0
         cent = torch.where(has[:, None], sums / cnt.clamp(min=1).to(x.dtype)[:, None], cent)
     return labels.to(torch.int32), cent, iterations
+
+
+# ------------------------------------------------------------------------ iSTFTNet head
+def istft_head_check(x, w, n_fft: int, hop: int):
+    """Shape rules of the iSTFTNet head; -> (x as [B, T, C], whether x came without a batch axis)."""
+    single = x.dim() == 2
+    xb = x.unsqueeze(0) if single else x
+    if xb.dim() != 3:
+        raise ValueError("istft_head: x must be [B, T, C] or [T, C]")
+    if n_fft < 2 or n_fft % 2 or hop < 1 or hop > n_fft:
+        raise ValueError(f"istft_head: n_fft {n_fft} / hop {hop}")
+    if w.dim() != 3 or tuple(w.shape) != (n_fft + 2, xb.shape[2], 7):
+        raise ValueError(f"istft_head: weight {tuple(w.shape)}, expected {(n_fft + 2, xb.shape[2], 7)}")
+    if xb.shape[1] < 2:
+        raise ValueError("istft_head: the reflection pad needs at least 2 rows per utterance")
+    return xb, single
+
+
+def istft_head(x, w, b, n_fft: int, hop: int, slope: float = 0.01):
+    """iSTFTNet head on last-stage rows x [B, T, C] (or [T, C]): leaky_relu(slope) -> one reflected row on the
+    left -> Conv1d(C, n_fft + 2, 7, padding 3) (w [n_fft + 2, C, 7], b [n_fft + 2]) -> mag = exp(first n_fft/2 + 1
+    channels), phase = sin(the others) -> inverse real DFT of each of the T + 1 frames, periodic Hann window ->
+    overlap-add at ``hop`` over the window envelope, the centred hop * T samples kept -> [B, hop * T] (or
+    [hop * T]).  The direct formula (a DFT-basis matmul and ``F.fold``, no FFT) in the dtype of x: in float64 it is
+    the oracle of the HIP kernel, and it equals ``torch.istft(mag * exp(i phase), n_fft, hop, n_fft, hann,
+    center=True)``.  Differentiable."""
+    xb, single = istft_head_check(x, w, n_fft, hop)
+    dt, dev = xb.dtype, xb.device
+    B, T, _ = xb.shape
+    N, H, nb = int(n_fft), int(hop), n_fft // 2 + 1
+    a = F.leaky_relu(xb, slope)
+    p = torch.cat([a[:, 1:2], a], 1)
+    z = F.conv1d(p.transpose(1, 2), w.to(dt), None if b is None else b.to(dt), padding=3)  # [B, N + 2, T + 1]
+    mag, phi = torch.exp(z[:, :nb]), torch.sin(z[:, nb:])
+    k = torch.arange(nb, device=dev, dtype=torch.float64)[:, None]
+    n = torch.arange(N, device=dev, dtype=torch.float64)[None, :]
+    ck = torch.full((nb, 1), 2.0, device=dev, dtype=torch.float64)
+    ck[0] = ck[nb - 1] = 1.0
+    ang = 2.0 * math.pi * k * n / N
+    win = 0.5 - 0.5 * torch.cos(2.0 * math.pi * n / N)  # periodic Hann [1, N]
+    bc = (ck * torch.cos(ang) * win / N).to(dt)  # [nb, N]
+    bs = (ck * torch.sin(ang) * win / N).to(dt)
+    re, im = mag * torch.cos(phi), mag * torch.sin(phi)  # [B, nb, F]
+    frames = torch.einsum("bkf,kn->bnf", re, bc) - torch.einsum("bkf,kn->bnf", im, bs)  # [B, N, F]
+    full = H * T + N  # H * (F - 1) + N
+    y = F.fold(frames, (1, full), (1, N), stride=(1, H)).reshape(B, full)
+    env = F.fold((win.to(dt) ** 2).reshape(1, N, 1).expand(1, N, T + 1), (1, full), (1, N),
+                 stride=(1, H)).reshape(1, full)
+    y = y[:, N // 2: N // 2 + H * T] / env[:, N // 2: N // 2 + H * T]
+    return y[0] if single else y

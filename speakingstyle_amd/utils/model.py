@@ -119,6 +119,9 @@ def get_vocoder(model_config, device, ckpt_dir: Optional[str] = None, allow_rand
     present (weights_only), otherwise random init (benchmarks).  MelGAN via
     torch.hub is not supported (network download).
 
+    ``vocoder.model: "iSTFTNet"`` builds the generator of ``config/hifigan/config_istft.json`` and loads
+    ``generator_istft_{speaker}.pth.tar`` under the same rule.
+
     ``vocoder.model: "GriffinLim"`` builds the checkpoint-free ``models.griffinlim.GriffinLim`` (optional
     ``vocoder.n_iters`` / ``vocoder.momentum``) for the STFT / mel settings of ``preprocess_config`` (default: the
     preprocessing defaults, 22.05 kHz / 1024 / 256 / 80 mels)."""
@@ -130,12 +133,16 @@ def get_vocoder(model_config, device, ckpt_dir: Optional[str] = None, allow_rand
         voc = model_config["vocoder"]
         pp = preprocess_config if preprocess_config is not None else normalize_preprocess_config(None)
         return GriffinLim(pp, n_iters=int(voc.get("n_iters", 60)), momentum=float(voc.get("momentum", 0.99)))
-    if name != "HiFi-GAN":
-        raise ValueError(f"vocoder {name!r} not supported (HiFi-GAN, GriffinLim)")
+    if name not in ("HiFi-GAN", "iSTFTNet"):
+        raise ValueError(f"vocoder {name!r} not supported (HiFi-GAN, iSTFTNet, GriffinLim)")
     speaker = model_config["vocoder"]["speaker"]
-    gen = Generator(vocoder_config())
     ckpt_dir = ckpt_dir or os.path.join(ROOT, "hifigan")
-    path = os.path.join(ckpt_dir, f"generator_{speaker}.pth.tar")
+    if name == "iSTFTNet":  # the C8C8I generator: two x8 upsamplers and an inverse-STFT head (models/hifigan.py)
+        gen = Generator(vocoder_config(os.path.join(ROOT, "config", "hifigan", "config_istft.json")))
+        path = os.path.join(ckpt_dir, f"generator_istft_{speaker}.pth.tar")
+    else:
+        gen = Generator(vocoder_config())
+        path = os.path.join(ckpt_dir, f"generator_{speaker}.pth.tar")
     if os.path.exists(path):
         ck = load_checkpoint(path)
         gen.load_state_dict(ck["generator"])

@@ -7,6 +7,7 @@ prosody control and GST style weights.
   word-level control: --word_pitch 1,1.3,0.8 --word_energy ... --word_duration ... (one factor per word)
   GST:     --style_weights 0.5,0,0,...   (one weight per style token)
   Griffin-Lim instead of HiFi-GAN (no vocoder checkpoint): --vocoder griffin_lim   (all modes)
+  iSTFTNet generator instead of HiFi-GAN (generator_istft_{speaker}.pth.tar): --vocoder istftnet   (all modes)
   serve:   python synthesize.py --mode serve [--source lines.txt] --restore_step N -p -m -t
            one text per line (from --source or stdin) -> {result_path}/serve_{line:04d}.wav, through the serving
            entry (infer/serve.py: bucketed HIP graphs on the GPU); prints the graph statistics at the end
@@ -36,9 +37,12 @@ def _floats(s):
 
 
 def _choose_vocoder(model_config, choice):
-    """--vocoder griffin_lim: the checkpoint-free Griffin-Lim vocoder instead of the model config's."""
+    """--vocoder griffin_lim: the checkpoint-free Griffin-Lim vocoder instead of the model config's;
+    --vocoder istftnet: the iSTFTNet generator (``generator_istft_{speaker}.pth.tar``, random init without one)."""
     if choice == "griffin_lim":
         model_config["vocoder"] = dict(model_config["vocoder"], model="GriffinLim")
+    elif choice == "istftnet":
+        model_config["vocoder"] = dict(model_config["vocoder"], model="iSTFTNet")
 
 
 def _transfer_args(args):
@@ -127,8 +131,9 @@ def main(argv=None):
     ap.add_argument("--batch_size", type=int, default=8)
     ap.add_argument("--plot", action="store_true", help="also write mel/pitch/energy PNGs")
     ap.add_argument("--result_path", type=str, default=None)
-    ap.add_argument("--vocoder", type=str, choices=["config", "griffin_lim"], default="config",
-                    help="config: the model config's vocoder (HiFi-GAN); griffin_lim: no checkpoint needed")
+    ap.add_argument("--vocoder", type=str, choices=["config", "griffin_lim", "istftnet"], default="config",
+                    help="config: the model config's vocoder (HiFi-GAN); griffin_lim: no checkpoint needed; "
+                         "istftnet: the iSTFTNet generator (config/hifigan/config_istft.json)")
     ap.add_argument("--prosody_ref", type=str, default=None,
                     help="a wav whose pitch / energy / timing the synthesis takes over; 'recording': each utterance's "
                          "own recording under raw_path (batch mode)")

@@ -4,7 +4,7 @@
 Reports achieved TFLOP/s (GEMM-shaped) or GB/s (memory-bound) per kernel, and
 the hipBLASLt number for the plain-GEMM equivalent (torch.matmul) as a yardstick.
 Usage (GPU box): python tools/bench_kernels.py [--rows 160000] [--iters 20] | --griffin-lim | --dtw | --align | --yin
-       | --pyin | --k256 | --prosody | --tsne | --features
+       | --pyin | --k256 | --prosody | --tsne | --features | --istftnet
 """
 import argparse
 import functools
@@ -953,6 +953,188 @@ def bench_features(out_path, rounds=9, iters=20, sr=22050, n_fft=1024, hop=256, 
             f.write(text)
 
 
+def _v1_tail_packed(g, x, vp, out, int16_scale):
+    """The part of HiFi-GAN V1's ``infer_packed`` that the iSTFT head stands in for: the stage 3 and 4 upsamplers and
+    MRFs and conv_post, on the packed rows x [R * 64, 128] after stage 2 (the launches ``Generator.infer_packed``
+    issues for i = 2, 3, copied from it)."""
+    from speakingstyle_amd.models import hifigan as H
+
+    nk, rate = g.num_kernels, 64
+    for i in (2, 3):
+        up = g.ups[i]
+        s = up.stride[0]
+        blocks = [g.resblocks[i * nk + j] for j in range(nk)]
+        wu, wimg, bt = g._ups_image(i)
+        cout = wu.shape[0] // s
+        fused = all(b.fusable(cout, vp.R * rate * s) for b in blocks)
+        x_act = None
+        if fused and H._CONV3_SQ[0] and bt is not None and wu.shape[0] == wu.shape[1] in (64, 128):
+            y = hip.conv3_sq_packed(x, vp, rate, wimg, bt)
+        else:
+            ks_ = (s // 2) * cout if (H._CONVT_KSPLIT[0] and up.kernel_size[0] == 2 * s
+                                      and up.padding[0] * 2 == s) else 0
+            if fused:
+                y = hip.conv1d_infer_packed(x, vp, rate, wu, bt, 1, 1, None, wimg=wimg, ksplit=ks_)
+            else:
+                y, x_act = hip.conv1d_infer_packed(x, vp, rate, wu, bt, 1, 1, None, wimg=wimg, dual_lrelu=True,
+                                                   ksplit=ks_)
+        rate *= s
+        y = y.view(vp.R * rate, cout)
+        if x_act is not None:
+            x_act = x_act.view(vp.R * rate, cout)
+        xs = None
+        for j, blk in enumerate(blocks):
+            last = j == nk - 1
+            xs = blk.forward_packed(y, vp, rate, acc=xs, out_scale=(1.0 / nk) if last else 1.0, x_act=x_act,
+                                    post_lrelu=(i < 3) and last)
+        x = xs
+    return hip.conv_post_packed(x, vp, rate, g.conv_post.weight, g.conv_post.bias, out, 0.01, int16_scale)
+
+
+def bench_istftnet(out_path, rounds=7, iters=10):
+    """iSTFTNet (C8C8I) against HiFi-GAN V1, random init, throughput at equal output length (not quality).
+    (1) The head kernel alone (csrc/k_istft.hip) on the last-stage rows of the 64-utterance LJSpeech-length batch,
+    padded and packed form, against its byte floor and against the V1 launches it stands in for (stage 3 / 4
+    upsamplers and ResBlocks + conv_post) on the same batch.  (2) ``Generator.infer_packed`` of both configs on the
+    same mel batches (256 utterances of LJSpeech lengths; 1 utterance of 113 frames), eager, and batch 1 through
+    the bucketed serving graphs.  Device events around ``iters`` calls after 3 warm-up calls, the arms alternating
+    round by round in one process; the ratios are taken per interleaved pair."""
+    import json as _json
+
+    import numpy as np
+
+    from speakingstyle_amd.data import synthetic
+    from speakingstyle_amd.models import hifigan as H
+
+    dev = torch.device("cuda")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    counts = synthetic.ljspeech_phone_counts(os.path.join(root, "preprocessed_data", "LJSpeech", "val.txt"))
+    rng = np.random.default_rng(0)
+    lens64 = np.clip(np.round(rng.choice(counts, size=64) * 8.1), 16, 1000).astype(np.int64).tolist()
+    lens256 = np.clip(np.round(rng.choice(counts, size=256) * 8.1), 16, 1000).astype(np.int64).tolist()
+    with open(os.path.join(root, "config", "hifigan", "config_istft.json")) as f:
+        hi = H.AttrDict(_json.load(f))
+    torch.manual_seed(0)
+    g1 = H.Generator(H.default_config()).eval().fold_weight_norm().to(dev).requires_grad_(False)
+    gi = H.Generator(hi).eval().fold_weight_norm().to(dev).requires_grad_(False)
+    HBM = 6.29e12  # measured streaming rate (8.0 TB/s spec)
+    lines = [f"iSTFTNet C8C8I vs HiFi-GAN V1, random init, bf16, {torch.cuda.get_device_name(0)}",
+             "throughput at equal output length (256 samples per mel frame); random weights say nothing about quality",
+             f"device events around {iters} calls after 3 warm-up calls; {rounds} rounds, the arms alternating in one "
+             "process; ms per call", ""]
+
+    def table(arms, title):
+        t = {a: [] for a, _ in arms}
+        for r in range(rounds):
+            for arm, fn in arms:
+                t[arm].append(timeit(fn, iters))
+        lines.append(title)
+        lines.append(f"{'arm':>52s} {'median':>10s} {'min':>10s} {'max':>10s}")
+        for arm, v in t.items():
+            lines.append(f"{arm:>52s} {'%10.4f %10.4f %10.4f' % _median_spread(v)}")
+        return t
+
+    def pairs(t, a, b, what):
+        r = sorted(x / y for x, y in zip(t[a], t[b]))
+        lines.append(f"{what}: {r[len(r) // 2]:.3f} at the median pair, {r[0]:.3f} .. {r[-1]:.3f} over the {len(r)} "
+                     f"interleaved pairs ({'above 1 in every pair' if r[0] > 1 else 'NOT above 1 in every pair'})")
+        return r
+
+    # ---- (1) the head kernel alone
+    C, rate = 128, 64
+    bm = hip.voc_tile_rows("istft", C)
+    R = sum(lens64)
+    rows = R * rate
+    torch.manual_seed(1)
+    x = torch.randn(rows, C, device=dev).to(torch.bfloat16)
+    w, b = gi.conv_post.weight, gi.conv_post.bias
+    vp = hip.voc_pack_for(lens64, dev, gi._packed_geoms(lens64))
+    vp1 = hip.voc_pack_for(lens64, dev, g1._packed_geoms(lens64))
+    Tm = max(lens64) * rate
+    xpad = torch.zeros(len(lens64), Tm, C, device=dev, dtype=torch.bfloat16)
+    o = 0
+    for u, n in enumerate(lens64):
+        xpad[u, : n * rate] = x[o * rate:(o + n) * rate]
+        o += n
+    out = torch.zeros(len(lens64), max(lens64) * 256, device=dev, dtype=torch.int16)
+    out1 = torch.zeros_like(out)
+    arms = (("istft_head_kernel, packed (int16 out)", lambda: hip.istft_head_packed(x, vp, rate, w, b, out, 32768.0)),
+            ("istft_head_kernel, padded (int16 out)", lambda: hip.istft_head(xpad, w, b, 32768.0)),
+            ("V1 stage 3 + 4 + conv_post, packed (int16 out)", lambda: _v1_tail_packed(g1, x, vp1, out1, 32768.0)))
+    t = table(arms, f"(1) head alone: 64 utterances, LJSpeech val lengths, {R} frames = {rows} last-stage rows x {C} "
+                    f"channels; tile {bm} rows, {sum(-(-n * rate // bm) for n in lens64)} workgroups packed, "
+                    f"{len(lens64) * -(-Tm // bm)} padded ({len(lens64) * Tm} padded rows)")
+    km = _median_spread(t["istft_head_kernel, packed (int16 out)"])[0]
+    kp = _median_spread(t["istft_head_kernel, padded (int16 out)"])[0]
+    byts = rows * C * 2 + 4 * rows * 2
+    floor_ms = byts / HBM * 1e3
+    flop = 2.0 * rows * (7 * C) * 18
+    lines += [f"byte floor: {rows} x {C} x 2 B read + 4 x {rows} x 2 B written = {byts / 1e6:.1f} MB at {HBM / 1e12:.2f} "
+              f"TB/s (measured streaming rate; 8.0 TB/s spec) = {floor_ms:.4f} ms; packed kernel {km:.4f} ms = "
+              f"{km / floor_ms:.2f} x the floor ({byts / (km * 1e-3) / 1e12:.2f} TB/s); padded {kp:.4f} ms for "
+              f"{len(lens64) * Tm * C * 2 / 1e6:.1f} MB of padded rows",
+              f"conv work: {flop / 1e9:.2f} GFLOP useful (N = 18), {flop * 32 / 18 * 2 / 1e9:.2f} GFLOP issued (N padded "
+              f"to 32, two sign halves) -> {flop * 32 / 18 * 2 / (km * 1e-3) / 1e12:.1f} TFLOP/s issued"]
+    pairs(t, "V1 stage 3 + 4 + conv_post, packed (int16 out)", "istft_head_kernel, packed (int16 out)",
+          "V1 stage 3 + 4 + conv_post / istft head (packed)")
+    lines += ["compile figures (gfx950) of istft_head_kernel<128, 16, 4>:"] + \
+             ["    " + s for s in _kernel_resources("k_istft.hip", "istft_head_kernelILi128E")] + [""]
+
+    # ---- (2) the generators, eager
+    torch.manual_seed(2)
+    mel256 = torch.randn(sum(lens256), 80, device=dev).to(torch.bfloat16)
+    mel1 = torch.randn(113, 80, device=dev).to(torch.bfloat16)
+    speed = {}
+    for name, mel, lens in (("batch 256, LJSpeech val lengths", mel256, lens256), ("batch 1, 113 frames", mel1, [113])):
+        arms = (("HiFi-GAN V1 infer_packed", lambda: g1.infer_packed(mel, lens, 32768.0)),
+                ("iSTFTNet C8C8I infer_packed", lambda: gi.infer_packed(mel, lens, 32768.0)))
+        t = table(arms, f"(2) Generator.infer_packed, eager, {name} ({sum(lens)} frames, {sum(lens) * 256 / 22050:.1f} s "
+                        "of audio)")
+        speed[name] = pairs(t, "HiFi-GAN V1 infer_packed", "iSTFTNet C8C8I infer_packed", "V1 / C8C8I")
+        mi = _median_spread(t["iSTFTNet C8C8I infer_packed"])[0]
+        m1 = _median_spread(t["HiFi-GAN V1 infer_packed"])[0]
+        lines += [f"RTF (vocoder only): V1 {m1 * 1e-3 / (sum(lens) * 256 / 22050):.3e}, C8C8I "
+                  f"{mi * 1e-3 / (sum(lens) * 256 / 22050):.3e}", ""]
+
+    # ---- (2b) batch 1 through the bucketed serving graphs (FastSpeech2 BC2013_GST + vocoder: the whole synthesis)
+    from speakingstyle_amd.config import load_named
+    from speakingstyle_amd.data.synthetic import SyntheticBatches
+    from speakingstyle_amd.infer.graphs import SynthGraphs
+    from speakingstyle_amd.models.fastspeech2 import FastSpeech2
+
+    pp, mc, tc = load_named("BC2013_GST")
+    torch.manual_seed(0)
+    model = FastSpeech2(pp, mc).to(dev)
+    with torch.no_grad():  # a duration head that speaks: ~8.1 frames per phoneme, 14 phonemes -> ~113 frames
+        lin = model.variance_adaptor.duration_predictor.linear_layer
+        lin.weight.normal_(0.0, 0.005)
+        lin.bias.fill_(math.log(9.1))
+    model.eval().set_compute_dtype(torch.bfloat16)
+    model.requires_grad_(False)
+    ref = SyntheticBatches(1, device=dev, seed=12, max_seq_len=mc["max_seq_len"],
+                           phone_counts=np.array([14])).make_batch()
+    ids = torch.from_numpy(np.random.default_rng(5).integers(1, 300, size=(1, 14)).astype(np.int64)).to(dev)
+    a = (ref[2][:1].contiguous(), ids, torch.tensor([14], device=dev), 14, ref[6][:1].contiguous(),
+         ref[7][:1].contiguous(), ref[8])
+    sgs = {"HiFi-GAN V1, graphs": SynthGraphs(model, g1, int16_scale=32768.0, warm=1, bucketed=True),
+           "iSTFTNet C8C8I, graphs": SynthGraphs(model, gi, int16_scale=32768.0, warm=1, bucketed=True)}
+    frames = {}
+    for k, sg in sgs.items():
+        for _ in range(4):  # warm, capture graph 1, capture graph 2, replay
+            frames[k] = sg(*a)[1]
+    arms = tuple((k, (lambda sg=sg: sg(*a))) for k, sg in sgs.items())
+    t = table(arms, f"(2b) text -> int16 wav through the bucketed graphs, batch 1, {sorted(set(sum(frames.values(), [])))} frames (FastSpeech2 "
+                    "BC2013_GST + vocoder, replays only)")
+    speed["graphs b1"] = pairs(t, "HiFi-GAN V1, graphs", "iSTFTNet C8C8I, graphs", "V1 / C8C8I (whole synthesis)")
+    lines += [f"graph statistics: {dict((k, dict(sg.stats)) for k, sg in sgs.items())}", ""]
+    text = "\n".join(lines) + "\n"
+    print(text, end="", flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
 def write_feature_corpus(root, n_utts=256, sr=22050, seed=0):
     """A synthetic raw corpus for the end-to-end preprocessing figure: ``n_utts`` int16 wavs with the LJSpeech
     ``val.txt`` length distribution (the signal of ``yin_workloads``) and a transcript each -> the config
@@ -1092,6 +1274,10 @@ def main():
                     help="only the feature front-end: the packed ops.frame_features launch vs the per-utterance loop over "
                          "hip.logmel and torch.stft + matmul (profiles/features.txt), then Preprocessor end to end, host "
                          "path vs device=\"cuda\" (profiles/preprocess_gpu.txt beside --out)")
+    ap.add_argument("--istftnet", action="store_true",
+                    help="iSTFTNet: the head kernel alone against its byte floor and the HiFi-GAN V1 launches it stands "
+                         "in for, then Generator.infer_packed V1 vs C8C8I, eager and through the bucketed graphs "
+                         "(profiles/istftnet.txt)")
     ap.add_argument("--preprocess-host-arm", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--out", default=None,
                     help="default: profiles/griffin_lim.txt, profiles/dtw.txt, profiles/align.txt, profiles/yin.txt, "
@@ -1100,6 +1286,8 @@ def main():
     prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
     if args.preprocess_host_arm:
         return preprocess_host_arm(args.preprocess_host_arm)
+    if args.istftnet:
+        return bench_istftnet(args.out or os.path.join(prof, "istftnet.txt"))
     if args.features:
         out = args.out or os.path.join(prof, "features.txt")
         bench_features(out)
